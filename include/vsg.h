@@ -122,6 +122,9 @@ typedef struct {
     uint64_t host_h2d_ns;              /*   query upload, */
     uint64_t host_device_ns;           /*   search kernels (prepare .. merge), */
     uint64_t host_d2h_ns;              /*   result download (HIP events on the call's stream) */
+    uint64_t search_sketch_rows;       /* sketch prefilter (vsg_index_set_prefilter): int8 sketch rows read ... */
+    uint64_t search_exact_rows;        /* ... and f32 rows read at level 0 by the prefiltered searches
+                                          (search_distances keeps counting every candidate) */
 } vsg_stats_t;
 
 /* replaces usearch::Index::new(&options) — src/index/usearch.rs:98 */
@@ -212,6 +215,17 @@ int vsg_index_exact_search(vsg_index_t* index, const float* queries, size_t nq, 
  * existing index; the f16 copy is built by the next search (and freed when
  * switched off).  VSG_EINVAL unless the storage is f32.  Not in usearch. */
 int vsg_index_set_f16_traversal(vsg_index_t* index, int enable);
+
+/* Sketch prefilter of the graph search (not in usearch; results are unchanged, bit for
+ * bit): a per-row int8 sketch (dimensions + 8 bytes per row, built by the next search,
+ * freed when switched off) gives a lower bound of a candidate's distance, and the f32
+ * row of a candidate the bound already rejects is not read.  Applies to f32 storage,
+ * cos / ip, rows of 1 to 8 KiB, ef <= 448, an index without removed entries, f16
+ * traversal off; every other search runs as before.  Until this is called the
+ * environment variable VSG_SEARCH_PREFILTER (0 / 1) decides, and when that is unset the
+ * prefilter runs where it measured faster: ef <= 64 and batches of >= 4096 queries.
+ * If the sketch cannot be allocated the search runs unfiltered and succeeds. */
+int vsg_index_set_prefilter(vsg_index_t* index, int on);
 
 /* Opt-in multi-entry descent (not usearch): upper_ef > 1 replaces the greedy
  * step on level 1 by a beam of width min(upper_ef, ef) whose whole result set

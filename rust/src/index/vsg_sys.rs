@@ -83,6 +83,8 @@ pub struct vsg_stats_t {
     pub host_h2d_ns: u64,
     pub host_device_ns: u64,
     pub host_d2h_ns: u64,
+    pub search_sketch_rows: u64,
+    pub search_exact_rows: u64,
 }
 
 /// The native actor's options (src/index/usearch.rs:60-66, 101-118 constants made knobs).
@@ -195,6 +197,7 @@ extern "C" {
                                  out_distances_device: *mut f32, stream: *mut c_void) -> c_int;
     pub fn vsg_index_set_f16_traversal(index: *mut vsg_index_t, enable: c_int) -> c_int;
     pub fn vsg_index_set_upper_ef(index: *mut vsg_index_t, upper_ef: usize) -> c_int;
+    pub fn vsg_index_set_prefilter(index: *mut vsg_index_t, on: c_int) -> c_int;
     pub fn vsg_index_stats(index: *const vsg_index_t, out: *mut vsg_stats_t) -> c_int;
     pub fn vsg_index_reset_stats(index: *mut vsg_index_t) -> c_int;
     pub fn vsg_index_graph_info(index: *const vsg_index_t, slots: *mut usize, upper_rows: *mut usize,

@@ -2,6 +2,8 @@
 // hnsw_search_reg_kernel and by the insert kernel); see hnsw_search_reg.hip
 // for the argument that it expands the same nodes as the sorted-list beam.
 #pragma once
+#include <type_traits>
+
 #include "hnsw_common.hpp"
 
 namespace vsg {
@@ -222,6 +224,29 @@ template <int R> struct RegSet {
         tkey = cut;
     }
 
+    // An upper bound of the ef-th smallest key (size >= ef): the radix select of
+    // compact() stopped after the top 16 bits of the distance word, the undecided
+    // bits set.  Nothing is moved.
+    __device__ __forceinline__ uint64_t bound_ef(int ef) const {
+        uint32_t ph = 0;
+        int need = ef;
+#pragma unroll 1
+        for (int b = 31; b >= 16; --b) {
+            const uint32_t hm = b == 31 ? 0u : (~0u << (b + 1));
+            int c = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const uint32_t hi = (uint32_t)(k[r] >> 32);
+                c += popc64(__ballot(k[r] != VSG_KEY_EMPTY && (hi & hm) == ph && !((hi >> b) & 1u)));
+            }
+            if (c < need) {
+                need -= c;
+                ph |= 1u << b;
+            }
+        }
+        return ((uint64_t)(ph | 0xFFFFu) << 32) | 0xFFFFFFFFull;
+    }
+
     // place the nc staged keys sk[0..nc) into free slots
     __device__ __forceinline__ void fill(const uint64_t* sk, int nc) {
         int acc = 0;
@@ -299,10 +324,28 @@ __device__ __forceinline__ void admit(RegSet<R>& B, bool mine, uint64_t ck, bool
 // (profiles/r06_c4_sq.json) -- latency is hidden by the other resident waves, so a
 // shorter chain per wave does not shorten the launch.  Not kept.
 // self: the node an insert (re)links, never admitted (VSG_EMPTY in searches).
-template <int G, int VM, int U, typename T, int MET, int R>
+//
+// Sketch prefilter (pre != nullptr, level 0 of the f32 dot-metric searches): before an
+// expansion's f32 rows are read, a lower bound of each fresh candidate's distance is
+// computed from its int8 sketch row (rows_sketch: 1 - (q . x~ + |q| err) <= the f32
+// distance the exact pass computes, sketch.hpp), and a candidate whose bound is not
+// below B.tkey is dropped: its exact key could not be admitted (admit: ck < tkey),
+// so B, the expansions and the results are those of the plain beam.  It still
+// counts in ndist.  For the bound to bite before the first compaction, tkey is
+// also lowered once per expansion to bound_ef(), an upper bound of the ef-th
+// smallest key of B: B is a superset of top_ef(S), so that key is the reference's
+// "worst of a full list", at or above which nothing is ever admitted.
+// PRE (hnsw_search_reg.hip: SketchPre, sketch_device.hpp) provides
+//   int filter(WaveLds& w, int cnt, uint64_t tkey)
+// which drops from w.todo[0..cnt) the ids it can reject and returns the survivors' count.
+struct NoSketch {};
+
+template <int G, int VM, int U, typename T, int MET, int R, typename PRE = NoSketch>
 __device__ __forceinline__ void beam_reg(const GraphDev& g, const QReg<G, VM, T>& q, int l, uint32_t ep, float dep, int ef, WaveLds& w,
-                         RegSet<R>& B, uint64_t& ndist, uint64_t& nadj, BeamProf& pf, uint32_t self = VSG_EMPTY) {
+                         RegSet<R>& B, uint64_t& ndist, uint64_t& nadj, BeamProf& pf, uint32_t self = VSG_EMPTY,
+                         PRE* pre = nullptr) {
     const int lane = lane_id();
+    [[maybe_unused]] int tau_size = -1;  // B.size at the last bound_ef()
     // select on values (readfirstlane), not on field addresses: a
     // select-of-loads folded into a load-of-select pinned the graph
     // descriptor in scratch inside the insert kernel
@@ -378,7 +421,7 @@ __device__ __forceinline__ void beam_reg(const GraphDev& g, const QReg<G, VM, T>
             if (nb != VSG_EMPTY && nb != self) fresh = w.vis.insert(nb, evicted);
             const uint64_t mask = __ballot(fresh);
             lossy = lossy || __ballot(evicted) != 0;
-            const int cnt = popc64(mask);
+            const int cnt0 = popc64(mask);
             if (fresh) w.todo[lanes_below(mask)] = nb;
             wave_sync();
             const uint64_t t1 = VSG_CLK();
@@ -390,6 +433,19 @@ __device__ __forceinline__ void beam_reg(const GraphDev& g, const QReg<G, VM, T>
                 c0c = c;
             }
 #endif
+            int cnt = cnt0;
+            if constexpr (!std::is_same<PRE, NoSketch>::value) {
+                if (cnt0) {  // pre is set whenever PRE is a filter
+                    if (B.size >= ef && B.size != tau_size) {
+                        const uint64_t tau = B.bound_ef(ef);
+                        if (tau < B.tkey) B.tkey = tau;
+                        tau_size = B.size;
+                    }
+                    if (B.tkey != VSG_KEY_EMPTY) cnt = pre->filter(w, cnt0, B.tkey);  // an open bound rejects nothing
+                    pre->nexact += (uint32_t)cnt;
+                }
+            }
+            ndist += (uint64_t)cnt0;
             if (cnt) {
 #ifdef VSG_SEARCH_PROFILE
                 rows_dist<G, VM, U, T, MET>(g.vecs, g.row_bytes, g.nchunks, w.todo, cnt, q, w.tdist, &pf.rows);
@@ -397,7 +453,6 @@ __device__ __forceinline__ void beam_reg(const GraphDev& g, const QReg<G, VM, T>
                 rows_dist<G, VM, U, T, MET>(g.vecs, g.row_bytes, g.nchunks, w.todo, cnt, q, w.tdist);
 #endif
                 wave_sync();
-                ndist += (uint64_t)cnt;
                 const uint64_t ck = lane < cnt ? cand_key(w.tdist[lane], w.todo[lane]) : VSG_KEY_EMPTY;
                 const uint64_t t2 = VSG_CLK();
                 pf.dist += t2 - t1;

@@ -35,6 +35,7 @@
 
 #include "hnsw_common.hpp"
 #include "hnsw_regset.hpp"
+#include "sketch_device.hpp"
 #include "vsg_dispatch.hpp"
 
 namespace vsg {
@@ -43,7 +44,8 @@ namespace vsg {
 #ifndef VSG_SEARCH_ATTR
 #define VSG_SEARCH_ATTR
 #endif
-template <int G, int VM, int U, typename T, int MET, int R>
+// PF: the sketch-prefilter instance (p.sk set; beam_reg, hnsw_regset.hpp)
+template <int G, int VM, int U, typename T, int MET, int R, bool PF>
 __device__ __forceinline__ void search_reg_one(const SearchParams& p, int qi, uint8_t* smem) {
     const int lane = lane_id();
     const GraphDev g = to_dev(p.g);
@@ -61,6 +63,20 @@ __device__ __forceinline__ void search_reg_one(const SearchParams& p, int qi, ui
         float dcur = dist_one<G, VM, U, T, MET>(g, q, cur, w);
         ++ndist;
         RegSet<R> B;
+        using SS = SketchShape<G, VM>;
+        using Pre = std::conditional_t<PF, SketchPre<SS::GS, SS::VMS, SS::US>, NoSketch>;
+        Pre pre_s;
+        Pre* pre = nullptr;
+        if constexpr (PF) {
+            pre_s.sk = p.sk;
+            pre_s.meta = reinterpret_cast<const float2*>(p.sk_meta);
+            pre_s.stride = p.sk_stride;
+            pre_s.schunks = (int)(p.sk_stride / 16);
+            // the query's sketch image: LDS after the visited table and the staging
+            pre_s.q.stage(p.queries + (size_t)qi * g.row_bytes, g.nchunks, p.sk_dim,
+                          smem + wave_lds_bytes(p.hash_size, 0, 0));
+            pre = &pre_s;
+        }
         if (p.upper_ef > 1 && p.max_level >= 1) {
             // opt-in multi-entry descent (not usearch): greedy down to level 2,
             // an upper_ef-wide beam on level 1, and its whole result set seeds
@@ -73,14 +89,20 @@ __device__ __forceinline__ void search_reg_one(const SearchParams& p, int qi, ui
             for (int l = p.max_level; l >= 2; --l) greedy_level<G, VM, U, T, MET>(g, q, l, cur, dcur, w, ndist, nadj);
             beam_reg<G, VM, U, T, MET, R>(g, q, 1, cur, dcur, min(p.upper_ef, p.ef), w, B, ndist, nadj, pf);
 #endif
-            beam_reg<G, VM, U, T, MET, R>(g, q, 0, VSG_EMPTY, 0.f, p.ef, w, B, ndist, nadj, pf);
+            beam_reg<G, VM, U, T, MET, R, Pre>(g, q, 0, VSG_EMPTY, 0.f, p.ef, w, B, ndist, nadj, pf, VSG_EMPTY, pre);
         } else {
             [[maybe_unused]] const uint64_t cd0 = VSG_CYC();
             for (int l = p.max_level; l >= 1; --l) greedy_level<G, VM, U, T, MET>(g, q, l, cur, dcur, w, ndist, nadj);
 #ifdef VSG_SEARCH_PROFILE
             pf.c_desc += VSG_CYC() - cd0;
 #endif
-            beam_reg<G, VM, U, T, MET, R>(g, q, 0, cur, dcur, p.ef, w, B, ndist, nadj, pf);
+            beam_reg<G, VM, U, T, MET, R, Pre>(g, q, 0, cur, dcur, p.ef, w, B, ndist, nadj, pf, VSG_EMPTY, pre);
+        }
+        if constexpr (PF) {
+            if (lane == 0 && p.stats) {
+                atomicAdd(&p.stats[18], (unsigned long long)pre_s.nsketch);
+                atomicAdd(&p.stats[19], (unsigned long long)pre_s.nexact);
+            }
         }
         // tombstones: skipped in the output, still traversed
         uint32_t alive = 0;
@@ -154,7 +176,7 @@ __device__ __forceinline__ void search_reg_one(const SearchParams& p, int qi, ui
 // the same constant.
 template <int G, int VM> constexpr bool persist_shape() { return G * VM * 16 >= 1024; }
 
-template <int G, int VM, int U, typename T, int MET, int R>
+template <int G, int VM, int U, typename T, int MET, int R, bool PF = false>
 __global__ __launch_bounds__(64) VSG_SEARCH_ATTR void hnsw_search_reg_kernel(SearchParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     if constexpr (persist_shape<G, VM>()) {
@@ -166,7 +188,7 @@ __global__ __launch_bounds__(64) VSG_SEARCH_ATTR void hnsw_search_reg_kernel(Sea
                 if (lane_id() == 0) qi = (int)atomicAdd(p.qnext, 1u);
                 qi = __builtin_amdgcn_readfirstlane(qi);
                 if (qi >= p.nq) break;
-                search_reg_one<G, VM, U, T, MET, R>(p, qi, smem);
+                search_reg_one<G, VM, U, T, MET, R, PF>(p, qi, smem);
                 wave_sync();
             }
             return;
@@ -178,11 +200,22 @@ __global__ __launch_bounds__(64) VSG_SEARCH_ATTR void hnsw_search_reg_kernel(Sea
         const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
         qi = x * qd + min(x, rm) + j;
     }
-    search_reg_one<G, VM, U, T, MET, R>(p, qi, smem);
+    search_reg_one<G, VM, U, T, MET, R, PF>(p, qi, smem);
+}
+
+// Instances of the sketch prefilter: f32 rows of 1 to 8 KiB, the dot metrics, and not the
+// 17-row class (ef > 448): with longer rows or that key set the variant no longer fits
+// two waves per SIMD.
+template <int G, int VM, typename T, int MET, int R> constexpr bool prefilter_shape() {
+    return std::is_same<T, float>::value && MET == MET_DOT && G * VM * 16 >= 1024 && G * VM <= 512 && R <= 8;
 }
 
 // slots per lane: 64 R >= ef + 64 (a compaction leaves room for a full batch)
 static inline int reg_rows(int ef) { return ef <= 64 ? 2 : ef <= 192 ? 4 : ef <= 448 ? 8 : 17; }
+
+bool search_prefilter_supported(Storage st, MetricKind mk, int nchunks, int ef) {
+    return st == ST_F32 && mk == MK_DOT && nchunks * 16 >= 1024 && nchunks <= 512 && ef >= 1 && ef <= 448;
+}
 
 size_t search_reg_lds_bytes(int hash) { return wave_lds_bytes(hash, 0, 0); }
 
@@ -212,7 +245,7 @@ static int resident_blocks(const void* kern, size_t lds) {
 hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, hipStream_t s) {
     if (p.nq <= 0) return hipSuccess;
     if (p.ef < 1 || p.ef > 1024 || p.k > p.ef || p.hash_size < p.k) return hipErrorInvalidValue;
-    const size_t lds = search_reg_lds_bytes(p.hash_size);
+    const size_t lds_plain = search_reg_lds_bytes(p.hash_size);
     hipError_t err = hipSuccess;
     // VSG_SEARCH_REG_ROWS (probes): more register rows than the minimum --
     // same results (B is any superset of the top ef), fewer compactions
@@ -229,7 +262,7 @@ hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, h
             constexpr int G = decltype(sh)::G, VM = decltype(sh)::VM, U = decltype(sh)::U;
             using T = typename decltype(tt)::T;
             constexpr int MET = decltype(mt)::MET;
-            auto run = [&](auto kern) {
+            auto run = [&](auto kern, size_t lds) {
                 if (lds > 65536)
                     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 constexpr int CH = 1 << 22;  // 64 work-items each: the AQL grid size is 32-bit
@@ -258,7 +291,14 @@ hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, h
                     err = hipGetLastError();
                 }
             };
-            run(hnsw_search_reg_kernel<G, VM, U, T, MET, R>);
+            // the sketch prefilter: f32 dot-metric rows of >= 1 KiB, 2 / 4 / 8 register rows
+            if constexpr (prefilter_shape<G, VM, T, MET, R>()) {
+                if (p.sk) {
+                    run(hnsw_search_reg_kernel<G, VM, U, T, MET, R, true>, lds_plain + SketchShape<G, VM>::LDS_BYTES);
+                    return;
+                }
+            }
+            run(hnsw_search_reg_kernel<G, VM, U, T, MET, R>, lds_plain);
         };
         // the search row shape (dispatch_shape_search): 4 passes for long rows with 2 register
         // rows (vsg_dispatch.hpp); with 17 (ef > 448) the generic shape, where the 8 x 2 shape

@@ -6,6 +6,7 @@
 // one-wave-per-row launch overflows beyond 2^32 / 64 = 67M rows (C4 is 100M).
 #include <hip/hip_runtime.h>
 
+#include "sketch.hpp"
 #include "vsg_device.hpp"
 #include "vsg_kernels.hpp"
 
@@ -268,6 +269,86 @@ hipError_t launch_datagen(int kind, size_t n, size_t dim, uint64_t seed, uint64_
         hipLaunchKernelGGL(gen_u8_kernel, dim3(capped_grid(tot, 256)), dim3(256), 0, s, n, (int)dim, seed,
                            start_row, out);
     }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------ int8 sketch --
+// f32 rows [r0, r1) -> sketch rows (sketch.hpp: bytes, and (scale, err) in meta).
+// One wave per row, one 4-element group per lane and step; the reductions are
+// wave-wide, the values those of sketch_row().
+__device__ __forceinline__ float wave_sum_f32(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ float wave_max_f32(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+__global__ __launch_bounds__(256) void sketch_rows_kernel(const uint8_t* __restrict__ vecs, size_t row_bytes, size_t r0,
+                                                          size_t r1, int dim, uint8_t* __restrict__ out, size_t stride,
+                                                          SketchMeta* __restrict__ meta) {
+    const int lane = threadIdx.x & 63;
+    const int ngroups = (dim + 3) / 4;          // 4-element groups holding the row (row_bytes >= 4 * dim rounded to 16)
+    const int sgroups = (int)(stride / 4);      // groups of the sketch row (>= ngroups)
+    for (size_t row = r0 + (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < r1; row += (size_t)gridDim.x * 4) {
+        const float4* src = reinterpret_cast<const float4*>(vecs + row * row_bytes);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(out + row * stride);
+        bool bad = false;
+        float mx = 0.f;
+        for (int g = lane; g < ngroups; g += 64) {
+            const float4 v = src[g];
+            const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (g * 4 + j < dim) {
+                    const float a = fabsf(e[j]);
+                    bad = bad || !(a <= 3.4028234e38f);
+                    mx = fmaxf(mx, a);
+                }
+            }
+        }
+        mx = wave_max_f32(mx);
+        const bool anybad = __ballot(bad) != 0;
+        const float scale = anybad ? 0.f : sketch_scale(mx);
+        float r2 = 0.f, x2 = 0.f;
+        for (int g = lane; g < sgroups; g += 64) {
+            uint32_t w = 0x80808080u;
+            if (scale > 0.f && g < ngroups) {
+                const float4 v = src[g];
+                const float e[4] = {v.x, v.y, v.z, v.w};
+                w = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    uint8_t u = 128;
+                    if (g * 4 + j < dim) {
+                        u = sketch_quant(e[j], scale);
+                        r2 += sketch_res2(e[j], scale, u);
+                        x2 = fmaf(e[j], e[j], x2);
+                    }
+                    w |= (uint32_t)u << (8 * j);
+                }
+            }
+            dst[g] = w;
+        }
+        r2 = wave_sum_f32(r2);
+        x2 = wave_sum_f32(x2);
+        if (lane == 0) {
+            SketchMeta m;
+            m.err = sketch_err(r2, x2, scale, dim);
+            m.scale = m.err < INFINITY ? scale : 0.f;
+            meta[row] = m;
+        }
+    }
+}
+
+hipError_t launch_sketch_rows(const uint8_t* vecs, size_t row_bytes, size_t r0, size_t r1, int dim, uint8_t* out,
+                              void* meta, hipStream_t s) {
+    if (r1 <= r0) return hipSuccess;
+    hipLaunchKernelGGL(sketch_rows_kernel, dim3(capped_grid(r1 - r0, 4)), dim3(256), 0, s, vecs, row_bytes, r0, r1, dim,
+                       out, sketch_stride(dim), reinterpret_cast<SketchMeta*>(meta));
     return hipGetLastError();
 }
 

@@ -29,6 +29,7 @@
 #include "../../include/vsg.h"
 #include "keymap.hpp"
 #include "roctx_range.hpp"
+#include "sketch.hpp"
 #include "vsg_kernels.hpp"
 
 namespace vsg {
@@ -443,6 +444,17 @@ struct vsg_index {
     uint8_t* d_vecs16 = nullptr;
     size_t shadow_cap = 0, shadow_rows = 0, row_bytes16 = 0;
     uint64_t shadow_gen = ~0ull;
+    // int8 sketch rows of the search prefilter (vsg_index_set_prefilter; sketch.hpp),
+    // maintained as the f16 copy is: built by the first eligible search, rows
+    // [0, sketch_rows) current for sketch_gen.  A row not converted yet has meta words
+    // of all ones (NaN: never rejected).  prefilter: -1 = the VSG_SEARCH_PREFILTER default.
+    int prefilter = -1;
+    std::mutex sketch_mu;
+    uint8_t* d_sketch = nullptr;
+    float* d_sketch_meta = nullptr;  // (scale, err) per row
+    size_t sketch_cap = 0, sketch_rows = 0;
+    uint64_t sketch_gen = ~0ull;
+    std::atomic<uint64_t> sketch_failures{0};  // searches that ran unfiltered because the copy failed
     // K-tiled copy of the f32 rows for the MFMA brute force of exact-only indexes
     // (MfmaExactParams::ktile): rows [0, ktile_rows) current for ktile_gen; kept up to
     // date by every add (ensure_ktile before publish) and, after rows move, by the
@@ -585,6 +597,7 @@ static void free_dev(vsg_index* h, PhaseClock* pc = nullptr) {
     h->ws_free.clear();
     mark("free:workspaces");
     for (void* p : {(void*)h->d_rm, (void*)h->d_reuse, (void*)h->d_lvl_all, (void*)h->d_vecs, (void*)h->d_vecs16,
+                    (void*)h->d_sketch, (void*)h->d_sketch_meta,
                     (void*)h->d_ktile, (void*)h->d_adj0, (void*)h->d_upper_off, (void*)h->d_upper,
                     (void*)h->d_adjd0, (void*)h->d_upperd, (void*)h->d_keys, (void*)h->d_flags,
                     (void*)h->d_sqnorm, (void*)h->d_stats, (void*)h->d_blevels, (void*)h->d_pair_off,
@@ -1823,6 +1836,11 @@ static int add_locked(vsg_index_t* h, const uint64_t* keys, const float* vecs, s
                 if (e != hipSuccess) h->vec_gen++;  // fall back to a full re-conversion
             }
         }
+        {
+            // the sketch rows of the rewritten slots are stale: rebuilt by the next search
+            std::lock_guard<std::mutex> g(h->sketch_mu);
+            h->sketch_gen = ~0ull;
+        }
         const hipError_t e = launch_set_flags(h->d_flags, reuse_view(h, r).slots, r, 0, h->stream);
         const hipError_t es = hipStreamSynchronize(h->stream);
         if (e != hipSuccess || es != hipSuccess)
@@ -2099,7 +2117,7 @@ static int ensure_shadow(vsg_index* h, hipStream_t s) {
             dev_free(h->d_vecs16, s);
             h->d_vecs16 = nullptr;
             h->shadow_cap = 0;
-            HIP_TRY(dev_alloc(&h->d_vecs16, h->cap * h->row_bytes16, h->stream));
+            HIP_TRY(dev_alloc(&h->d_vecs16, h->cap * h->row_bytes16, s));  // on the stream that fills it
             h->shadow_cap = h->cap;
         }
         // zeros past the published rows: a search beside a build may reach rows of
@@ -2117,6 +2135,67 @@ static int ensure_shadow(vsg_index* h, hipStream_t s) {
         h->shadow_rows = slots;
     }
     return VSG_OK;
+}
+
+// The sketch prefilter applies to unfiltered graph searches of f32 dot-metric rows of
+// 1-8 KiB outside the f16-traversal mode.  vsg_index_set_prefilter / VSG_SEARCH_PREFILTER
+// (0 / 1) decide where they are set; otherwise it runs where it was measured faster:
+// ef <= 64 (the 2-row register class) and batches of >= 4,096 queries, which oversubscribe
+// the resident waves so that bytes, not one query's chain of round trips, set the time
+// (C2, ef 36: 10k queries 2.84 -> 2.42 ms, 512 queries 0.42 -> 0.58 ms; ef 128: 10k
+// 5.07 -> 5.70 ms; profiles/prefilter_fractions.jsonl).
+static bool prefilter_on(const vsg_index* h, size_t ef, size_t nq) {
+    if (h->f16_trav || !search_prefilter_supported(h->st, h->mk, h->nchunks, (int)ef)) return false;
+    if (h->prefilter >= 0) return h->prefilter != 0;
+    if (const char* e = getenv("VSG_SEARCH_PREFILTER")) return atof(e) != 0;
+    return ef <= 64 && nq >= 4096;
+}
+
+// Bring the sketch rows up to date (caller holds h->mu shared), as ensure_shadow does
+// for the f16 copy: only [sketch_rows, slots) is converted between vec_gen bumps.
+// Rows past the converted ones -- the tail of the capacity, the batch a concurrent
+// build is writing -- keep meta words of all ones, which no candidate is rejected on.
+// Returns false when the copy is not available (allocation or launch failure): the
+// search then runs the plain kernel.
+static bool ensure_sketch(vsg_index* h, hipStream_t s) {
+    std::lock_guard<std::mutex> g(h->sketch_mu);
+    if (env_double("VSG_TEST_FAIL_SKETCH", 0) != 0) return false;  // fault injection (tests only)
+    const size_t slots = h->pub_slots;
+    const size_t stride = sketch_stride(h->dim);
+    if (h->sketch_gen != h->vec_gen || h->sketch_cap < slots || h->sketch_rows > slots) {
+        if (h->sketch_cap < h->cap) {
+            h->fence.drain();  // device searches enqueued earlier may read the old rows
+            dev_free(h->d_sketch, s);
+            dev_free(h->d_sketch_meta, s);
+            h->d_sketch = nullptr;
+            h->d_sketch_meta = nullptr;
+            h->sketch_cap = h->sketch_rows = 0;
+            h->sketch_gen = ~0ull;
+            if (dev_alloc(&h->d_sketch, h->cap * stride, s) != hipSuccess ||
+                dev_alloc(&h->d_sketch_meta, h->cap * 2, s) != hipSuccess) {
+                (void)hipGetLastError();
+                dev_free(h->d_sketch, s);
+                dev_free(h->d_sketch_meta, s);
+                h->d_sketch = nullptr;
+                h->d_sketch_meta = nullptr;
+                return false;
+            }
+            h->sketch_cap = h->cap;
+        }
+        if (hipMemsetAsync(h->d_sketch_meta, 0xFF, h->sketch_cap * 2 * sizeof(float), s) != hipSuccess) return false;
+        h->sketch_rows = 0;
+        h->sketch_gen = h->vec_gen;
+    }
+    if (h->sketch_rows < slots) {
+        if (launch_sketch_rows(h->d_vecs, h->row_bytes, h->sketch_rows, slots, h->dim, h->d_sketch, h->d_sketch_meta,
+                               s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            h->sketch_gen = ~0ull;  // redone from row 0 by the next search
+            return false;
+        }
+        h->sketch_rows = slots;
+    }
+    return true;
 }
 
 // The K-tiled MFMA copy applies to exact-only f32 indexes whose rows are whole
@@ -2143,7 +2222,7 @@ static int ensure_ktile(vsg_index* h, size_t slots, hipStream_t s) {
             dev_free(h->d_ktile, s);
             h->d_ktile = nullptr;
             h->ktile_cap = 0;
-            HIP_TRY(dev_alloc(&h->d_ktile, want_cap * (h->row_bytes / 4), h->stream));
+            HIP_TRY(dev_alloc(&h->d_ktile, want_cap * (h->row_bytes / 4), s));  // on the stream that fills it
             // padding rows of the last tile are read (clamped loads never, but keep them defined)
             HIP_TRY(hipMemsetAsync(h->d_ktile, 0, want_cap * h->row_bytes, s));
             h->ktile_cap = want_cap;
@@ -2385,6 +2464,18 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
             // as one that did not; multi-entry descent applies to
             // indexes without removed entries
             p.upper_ef = 0;
+        }
+        // int8 sketch prefilter (same results, fewer f32 rows read): the register kernel,
+        // no removed entries
+        if (!rerank && !filt && p.reg && slots > 0 && prefilter_on(h, e, nq)) {
+            if (ensure_sketch(h, s)) {
+                p.sk = h->d_sketch;
+                p.sk_meta = h->d_sketch_meta;
+                p.sk_stride = sketch_stride(h->dim);
+                p.sk_dim = h->dim;
+            } else {
+                h->sketch_failures++;
+            }
         }
         if (!rerank) {
             err = launch_search(h->st, h->mk, p, s);
@@ -2751,6 +2842,25 @@ int vsg_index_set_upper_ef(vsg_index_t* h, size_t upper_ef) {
     return VSG_OK;
 }
 
+int vsg_index_set_prefilter(vsg_index_t* h, int on) {
+    VSG_RANGE();
+    if (!h) return fail(VSG_EINVAL, "null index");
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    DeviceGuard dg(h->device);
+    std::lock_guard<std::mutex> g(h->sketch_mu);
+    h->prefilter = on != 0;
+    if (!on && h->d_sketch) {
+        h->fence.drain();  // device searches enqueued earlier may still read the rows
+        dev_free(h->d_sketch, h->stream);
+        dev_free(h->d_sketch_meta, h->stream);
+        h->d_sketch = nullptr;
+        h->d_sketch_meta = nullptr;
+        h->sketch_cap = h->sketch_rows = 0;
+        h->sketch_gen = ~0ull;
+    }
+    return VSG_OK;
+}
+
 int vsg_index_set_f16_traversal(vsg_index_t* h, int enable) {
     VSG_RANGE();
     if (!h) return fail(VSG_EINVAL, "null index");
@@ -2854,6 +2964,8 @@ int vsg_index_stats(const vsg_index_t* h, vsg_stats_t* out) {
     out->host_h2d_ns = h->hs_h2d_ns.load();
     out->host_device_ns = h->hs_dev_ns.load();
     out->host_d2h_ns = h->hs_d2h_ns.load();
+    out->search_sketch_rows = s[18];
+    out->search_exact_rows = s[19];
     return VSG_OK;
 }
 

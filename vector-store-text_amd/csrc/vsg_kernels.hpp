@@ -57,6 +57,14 @@ struct SearchParams {
     // waves pulling query indices from this counter (zeroed per launch); nullptr:
     // one workgroup per query
     unsigned* qnext;
+    // Sketch prefilter (register kernel, f32 dot-metric rows >= 1 KiB; sketch.hpp): the
+    // int8 sketch rows (sk_stride bytes each) and their (scale, err) pairs.  nullptr:
+    // the plain kernel.  Same results either way; stats [18] / [19] count the sketch
+    // rows read and the f32 rows read at level 0.
+    const uint8_t* sk;
+    const void* sk_meta;
+    size_t sk_stride;
+    int sk_dim;
 };
 
 struct InsertParams {
@@ -169,7 +177,7 @@ struct RerankParams {
 };
 
 // kernel counter block (d_stats): [0..2] search, [3..9] build, [10..15] wave
-// clocks (tools), [16] filtered-search overflow
+// clocks (tools), [16] filtered-search overflow, [18] / [19] sketch / f32 rows of the prefiltered search
 constexpr int VSG_NSTATS = 32;
 
 // key layout of the reverse-link pairs
@@ -224,6 +232,12 @@ hipError_t launch_shadow_f16(const uint8_t* vecs, size_t row_bytes, size_t r0, s
 // rows `slots[0..n)` (those < limit) of the f16 traversal copy, re-converted in place
 hipError_t launch_shadow_f16_slots(const uint8_t* vecs, size_t row_bytes, const uint32_t* slots, size_t n,
                                    size_t limit, int dim, uint8_t* out, size_t row_bytes16, hipStream_t s);
+// f32 image rows [r0, r1) -> int8 sketch rows (sketch.hpp; sketch_stride(dim) bytes each)
+// and their SketchMeta (scale, err)
+hipError_t launch_sketch_rows(const uint8_t* vecs, size_t row_bytes, size_t r0, size_t r1, int dim, uint8_t* out,
+                              void* meta, hipStream_t s);
+// the sketch prefilter has an instance for this search (f32 dot-metric rows of 1 to 8 KiB, ef <= 448)
+bool search_prefilter_supported(Storage st, MetricKind mk, int nchunks, int ef);
 // rows [r0, r1) of row-major f32 `vecs` (row_floats % 32 == 0) -> the K-tiled layout
 // of MfmaExactParams::ktile
 hipError_t launch_ktile_rows(const float* vecs, int row_floats, size_t r0, size_t r1, float* ktile,

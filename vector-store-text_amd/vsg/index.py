@@ -203,6 +203,11 @@ class Index:
         (0/1 = usearch greedy descent, the default)."""
         check(lib().vsg_index_set_upper_ef(self._h, int(upper_ef)))
 
+    def set_prefilter(self, on: bool) -> None:
+        """Sketch prefilter of the graph search (same results; on by default where it
+        applies: f32 cos / ip rows of >= 1 KiB; csrc/sketch.hpp)."""
+        check(lib().vsg_index_set_prefilter(self._h, 1 if on else 0))
+
     def reset_stats(self) -> None:
         check(lib().vsg_index_reset_stats(self._h))
 
