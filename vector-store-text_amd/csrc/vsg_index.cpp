@@ -29,6 +29,7 @@
 #include "../../include/vsg.h"
 #include "keymap.hpp"
 #include "roctx_range.hpp"
+#include "search_plan.hpp"
 #include "sketch.hpp"
 #include "vsg_kernels.hpp"
 
@@ -407,6 +408,16 @@ struct SearchFence {
     }
 };
 
+// Upkeep state of one derived copy of the rows (the f16 traversal copy, the int8 sketch,
+// the K-tiled MFMA copy): rows are append-only between vec_gen bumps, so a copy whose
+// gen equals vec_gen is current for rows [0, rows) and only the rest is converted.
+// The device pointers live beside each instance in vsg_index.
+struct RowCopy {
+    std::mutex mu;
+    size_t cap = 0, rows = 0;  // rows allocated / converted
+    uint64_t gen = ~0ull;      // ~0: stale, converted from row 0 by the next ensure
+};
+
 struct vsg_index {
     vsg_index_options_t opt{};
     int dim = 0;
@@ -436,33 +447,29 @@ struct vsg_index {
     float* d_sqnorm = nullptr;  // |stored row|^2 (MFMA exact L2 expansion)
     uint64_t vec_gen = 0;       // bumped when rows are rewritten or moved (shadow invalidation)
 
+    // Three derived copies of the rows, each kept current by row_copy_ensure (below):
+    // rows [0, rows) of a RowCopy are current for generation gen.
     // f16 traversal copy (vsg_index_set_f16_traversal; rerank.hip): built lazily by
-    // the first search after rows change, rows [0, shadow_rows) current for shadow_gen
+    // the first search after rows change
     bool f16_trav = false;
     int upper_ef = 0;  // vsg_index_set_upper_ef: > 1 = multi-entry descent (opt-in)
-    std::mutex shadow_mu;
+    RowCopy shadow;
     uint8_t* d_vecs16 = nullptr;
-    size_t shadow_cap = 0, shadow_rows = 0, row_bytes16 = 0;
-    uint64_t shadow_gen = ~0ull;
+    size_t row_bytes16 = 0;
     // int8 sketch rows of the search prefilter (vsg_index_set_prefilter; sketch.hpp),
-    // maintained as the f16 copy is: built by the first eligible search, rows
-    // [0, sketch_rows) current for sketch_gen.  A row not converted yet has meta words
-    // of all ones (NaN: never rejected).  prefilter: -1 = the VSG_SEARCH_PREFILTER default.
+    // maintained as the f16 copy is: built by the first eligible search.  A row not
+    // converted yet has meta words of all ones (NaN: never rejected).
+    // prefilter: -1 = the VSG_SEARCH_PREFILTER default.
     int prefilter = -1;
-    std::mutex sketch_mu;
+    RowCopy sketch;
     uint8_t* d_sketch = nullptr;
     float* d_sketch_meta = nullptr;  // (scale, err) per row
-    size_t sketch_cap = 0, sketch_rows = 0;
-    uint64_t sketch_gen = ~0ull;
     std::atomic<uint64_t> sketch_failures{0};  // searches that ran unfiltered because the copy failed
     // K-tiled copy of the f32 rows for the MFMA brute force of exact-only indexes
-    // (MfmaExactParams::ktile): rows [0, ktile_rows) current for ktile_gen; kept up to
-    // date by every add (ensure_ktile before publish) and, after rows move, by the
-    // next exact search
-    std::mutex ktile_mu;
+    // (MfmaExactParams::ktile): kept up to date by every add (ensure_ktile before
+    // publish) and, after rows move, by the next exact search
+    RowCopy ktile;
     float* d_ktile = nullptr;
-    size_t ktile_cap = 0, ktile_rows = 0;
-    uint64_t ktile_gen = ~0ull;
     std::atomic<uint64_t> ktile_failures{0};  // adds whose K-tiled copy failed (finished by the next exact search)
     // host-buffer searches: count, wall ns, and (VSG_PROFILE_HOST_SEARCH=1) device-timeline split
     std::atomic<uint64_t> hs_calls{0}, hs_ns{0}, hs_h2d_ns{0}, hs_dev_ns{0}, hs_d2h_ns{0};
@@ -571,6 +578,53 @@ struct vsg_index {
         return g;
     }
 };
+
+// Free a derived copy's blocks (ordered on stream s) and mark it stale.  Device
+// searches enqueued earlier may still read them: wait for those first.  Caller holds c.mu.
+template <typename... P>
+static void row_copy_drop(vsg_index* h, RowCopy& c, hipStream_t s, P*&... blocks) {
+    h->fence.drain();
+    ((dev_free(blocks, s), blocks = nullptr), ...);
+    c.cap = c.rows = 0;
+    c.gen = ~0ull;
+}
+
+// Rows were rewritten in place: the next ensure converts the copy from row 0.
+static void row_copy_mark_stale(RowCopy& c) {
+    std::lock_guard<std::mutex> g(c.mu);
+    c.gen = ~0ull;
+}
+
+// The upkeep the derived copies share (caller holds c.mu, and h->mu at least shared):
+// bring rows [0, slots) of copy c up to date on stream s.
+//   1. stale (generation mismatch, capacity short, or more rows converted than are
+//      published): when the capacity is short, realloc(want_cap, s) drops the old
+//      blocks (row_copy_drop) and allocates new ones on s, the stream that fills them;
+//      then reset(slots, s), and the copy restarts from row 0;
+//   2. convert(first, last, s) for the rows not converted yet, then wait for s: another
+//      stream's search may read the copy as soon as c.mu is released.
+// want_cap follows h->cap, which grows only with a vec_gen bump (reserve_locked).
+// A new derived copy is these three callables, not another state machine.
+template <typename Realloc, typename Reset, typename Convert>
+static hipError_t row_copy_ensure(vsg_index* h, RowCopy& c, size_t want_cap, size_t slots, hipStream_t s,
+                                  Realloc realloc, Reset reset, Convert convert) {
+    hipError_t e;
+    if (c.gen != h->vec_gen || c.cap < want_cap || c.rows > slots) {
+        if (c.cap < want_cap) {
+            if ((e = realloc(want_cap, s)) != hipSuccess) return e;
+            c.cap = want_cap;
+        }
+        if ((e = reset(slots, s)) != hipSuccess) return e;
+        c.rows = 0;
+        c.gen = h->vec_gen;
+    }
+    if (c.rows < slots) {
+        if ((e = convert(c.rows, slots, s)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+        c.rows = slots;
+    }
+    return hipSuccess;
+}
 
 // Everything the index owns goes back: device buffers to the pool, ordered on
 // the index's stream (the caller drained the device-search fence and the stream's
@@ -1828,19 +1882,16 @@ static int add_locked(vsg_index_t* h, const uint64_t* keys, const float* vecs, s
         // rows re-converted (round 5 marked the whole copy stale, so the next search
         // converted every row)
         {
-            std::lock_guard<std::mutex> g(h->shadow_mu);
-            if (h->d_vecs16 && h->shadow_gen == h->vec_gen && h->shadow_rows > 0) {
+            std::lock_guard<std::mutex> g(h->shadow.mu);
+            if (h->d_vecs16 && h->shadow.gen == h->vec_gen && h->shadow.rows > 0) {
                 const hipError_t e = launch_shadow_f16_slots(h->d_vecs, h->row_bytes, reuse_view(h, r).slots, r,
-                                                             h->shadow_rows, h->dim, h->d_vecs16, h->row_bytes16,
+                                                             h->shadow.rows, h->dim, h->d_vecs16, h->row_bytes16,
                                                              h->stream);
                 if (e != hipSuccess) h->vec_gen++;  // fall back to a full re-conversion
             }
         }
-        {
-            // the sketch rows of the rewritten slots are stale: rebuilt by the next search
-            std::lock_guard<std::mutex> g(h->sketch_mu);
-            h->sketch_gen = ~0ull;
-        }
+        // the sketch rows of the rewritten slots are stale: rebuilt by the next search
+        row_copy_mark_stale(h->sketch);
         const hipError_t e = launch_set_flags(h->d_flags, reuse_view(h, r).slots, r, 0, h->stream);
         const hipError_t es = hipStreamSynchronize(h->stream);
         if (e != hipSuccess || es != hipSuccess)
@@ -1849,7 +1900,7 @@ static int add_locked(vsg_index_t* h, const uint64_t* keys, const float* vecs, s
     }
     // exact-only f32: the K-tiled MFMA copy of the new rows.  The add is committed
     // either way (rows, keys, live count): a copy that failed is not an add that
-    // failed -- the next exact search completes it (ktile_rows < slots), so the
+    // failed -- the next exact search completes it (ktile.rows < slots), so the
     // call reports success and the failure only in the stats (a
     // client retrying a "failed" add would have turned it into a replace).
     if (ktile_on(h) && ensure_ktile(h, h->slots, h->stream) != VSG_OK) h->ktile_failures++;
@@ -2021,8 +2072,6 @@ int vsg_index_replace_device(vsg_index_t* h, const uint64_t* keys, const float* 
     return replace_common(h, keys, vectors_device, n, batch, 0, status, nullptr, true, (hipStream_t)stream);
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Up to WS_MAX searches on different streams run concurrently, each in its own
 // scratch set: a workspace last used on another stream whose search is still
 // running is reused only once WS_MAX exist (then the new search waits for it).
@@ -2106,35 +2155,42 @@ static void ws_release(vsg_index* h, Workspace* w, hipStream_t s) {
     h->ws_free.push_back(w);
 }
 
-// Bring the f16 traversal copy up to date (caller holds h->mu shared): rows are
-// append-only between vec_gen bumps, so only [shadow_rows, slots) is converted.
+// HIP_TRY inside a callable of row_copy_ensure: the failing expression's text goes to
+// `step`, from which the copies whose failures are hard make HIP_TRY's message
+#define ROW_TRY(expr)                                          \
+    do {                                                       \
+        if (hipError_t e__ = (expr)) return step = #expr, e__; \
+    } while (0)
+static int row_copy_fail(const char* step, hipError_t e) {
+    return fail(VSG_EDEVICE, std::string(step) + ": " + hipGetErrorString(e));
+}
+
+// Bring the f16 traversal copy up to date (caller holds h->mu shared).
 static int ensure_shadow(vsg_index* h, hipStream_t s) {
-    std::lock_guard<std::mutex> g(h->shadow_mu);
-    const size_t slots = h->pub_slots;
-    if (h->shadow_gen != h->vec_gen || h->shadow_cap < slots || h->shadow_rows > slots) {
-        if (h->shadow_cap < h->cap) {
-            h->fence.drain();  // device searches enqueued earlier may walk the old copy
-            dev_free(h->d_vecs16, s);
-            h->d_vecs16 = nullptr;
-            h->shadow_cap = 0;
-            HIP_TRY(dev_alloc(&h->d_vecs16, h->cap * h->row_bytes16, s));  // on the stream that fills it
-            h->shadow_cap = h->cap;
-        }
-        // zeros past the published rows: a search beside a build may reach rows of
-        // the batch in flight before they are converted (their f32 re-rank is exact
-        // either way); after a compaction those rows still hold pre-compaction images
-        if (h->shadow_cap > slots)
-            HIP_TRY(hipMemsetAsync(h->d_vecs16 + slots * h->row_bytes16, 0, (h->shadow_cap - slots) * h->row_bytes16, s));
-        h->shadow_rows = 0;
-        h->shadow_gen = h->vec_gen;
-    }
-    if (h->shadow_rows < slots) {
-        HIP_TRY(launch_shadow_f16(h->d_vecs, h->row_bytes, h->shadow_rows, slots, h->dim, h->d_vecs16,
-                                  h->row_bytes16, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        h->shadow_rows = slots;
-    }
-    return VSG_OK;
+    RowCopy& c = h->shadow;
+    std::lock_guard<std::mutex> g(c.mu);
+    const char* step = "hipStreamSynchronize(s)";
+    const hipError_t e = row_copy_ensure(
+        h, c, h->cap, h->pub_slots, s,
+        [&](size_t, hipStream_t s) {
+            row_copy_drop(h, c, s, h->d_vecs16);  // device searches enqueued earlier may walk the old copy
+            ROW_TRY(dev_alloc(&h->d_vecs16, h->cap * h->row_bytes16, s));
+            return hipSuccess;
+        },
+        [&](size_t slots, hipStream_t s) {
+            // zeros past the published rows: a search beside a build may reach rows of
+            // the batch in flight before they are converted (their f32 re-rank is exact
+            // either way); after a compaction those rows still hold pre-compaction images
+            if (h->shadow.cap > slots)
+                ROW_TRY(hipMemsetAsync(h->d_vecs16 + slots * h->row_bytes16, 0, (h->shadow.cap - slots) * h->row_bytes16, s));
+            return hipSuccess;
+        },
+        [&](size_t, size_t slots, hipStream_t s) {  // from h->shadow.rows
+            ROW_TRY(launch_shadow_f16(h->d_vecs, h->row_bytes, h->shadow.rows, slots, h->dim, h->d_vecs16,
+                                      h->row_bytes16, s));
+            return hipSuccess;
+        });
+    return e == hipSuccess ? VSG_OK : row_copy_fail(step, e);
 }
 
 // The sketch prefilter applies to unfiltered graph searches of f32 dot-metric rows of
@@ -2151,51 +2207,33 @@ static bool prefilter_on(const vsg_index* h, size_t ef, size_t nq) {
     return ef <= 64 && nq >= 4096;
 }
 
-// Bring the sketch rows up to date (caller holds h->mu shared), as ensure_shadow does
-// for the f16 copy: only [sketch_rows, slots) is converted between vec_gen bumps.
-// Rows past the converted ones -- the tail of the capacity, the batch a concurrent
-// build is writing -- keep meta words of all ones, which no candidate is rejected on.
+// Bring the sketch rows up to date (caller holds h->mu shared).  Rows past the
+// converted ones -- the tail of the capacity, the batch a concurrent build is
+// writing -- keep meta words of all ones, which no candidate is rejected on.
 // Returns false when the copy is not available (allocation or launch failure): the
 // search then runs the plain kernel.
 static bool ensure_sketch(vsg_index* h, hipStream_t s) {
-    std::lock_guard<std::mutex> g(h->sketch_mu);
+    RowCopy& c = h->sketch;
+    std::lock_guard<std::mutex> g(c.mu);
     if (env_double("VSG_TEST_FAIL_SKETCH", 0) != 0) return false;  // fault injection (tests only)
-    const size_t slots = h->pub_slots;
-    const size_t stride = sketch_stride(h->dim);
-    if (h->sketch_gen != h->vec_gen || h->sketch_cap < slots || h->sketch_rows > slots) {
-        if (h->sketch_cap < h->cap) {
-            h->fence.drain();  // device searches enqueued earlier may read the old rows
-            dev_free(h->d_sketch, s);
-            dev_free(h->d_sketch_meta, s);
-            h->d_sketch = nullptr;
-            h->d_sketch_meta = nullptr;
-            h->sketch_cap = h->sketch_rows = 0;
-            h->sketch_gen = ~0ull;
-            if (dev_alloc(&h->d_sketch, h->cap * stride, s) != hipSuccess ||
-                dev_alloc(&h->d_sketch_meta, h->cap * 2, s) != hipSuccess) {
+    const hipError_t e = row_copy_ensure(
+        h, c, h->cap, h->pub_slots, s,
+        [&](size_t cap, hipStream_t s) {
+            row_copy_drop(h, c, s, h->d_sketch, h->d_sketch_meta);  // earlier device searches may read the old rows
+            hipError_t a = dev_alloc(&h->d_sketch, cap * sketch_stride(h->dim), s);
+            if (a == hipSuccess) a = dev_alloc(&h->d_sketch_meta, cap * 2, s);
+            if (a != hipSuccess) {
                 (void)hipGetLastError();
-                dev_free(h->d_sketch, s);
-                dev_free(h->d_sketch_meta, s);
-                h->d_sketch = nullptr;
-                h->d_sketch_meta = nullptr;
-                return false;
+                row_copy_drop(h, c, s, h->d_sketch, h->d_sketch_meta);
             }
-            h->sketch_cap = h->cap;
-        }
-        if (hipMemsetAsync(h->d_sketch_meta, 0xFF, h->sketch_cap * 2 * sizeof(float), s) != hipSuccess) return false;
-        h->sketch_rows = 0;
-        h->sketch_gen = h->vec_gen;
-    }
-    if (h->sketch_rows < slots) {
-        if (launch_sketch_rows(h->d_vecs, h->row_bytes, h->sketch_rows, slots, h->dim, h->d_sketch, h->d_sketch_meta,
-                               s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            h->sketch_gen = ~0ull;  // redone from row 0 by the next search
-            return false;
-        }
-        h->sketch_rows = slots;
-    }
-    return true;
+            return a;
+        },
+        [&](size_t, hipStream_t s) { return hipMemsetAsync(h->d_sketch_meta, 0xFF, c.cap * 2 * sizeof(float), s); },
+        [&](size_t first, size_t last, hipStream_t s) {
+            return launch_sketch_rows(h->d_vecs, h->row_bytes, first, last, h->dim, h->d_sketch, h->d_sketch_meta, s);
+        });
+    if (e != hipSuccess) c.gen = ~0ull;  // redone from row 0 by the next search
+    return e == hipSuccess;
 }
 
 // The K-tiled MFMA copy applies to exact-only f32 indexes whose rows are whole
@@ -2205,40 +2243,256 @@ static bool ktile_on(const vsg_index* h) {
            env_double("VSG_EXACT_KTILE", 1) != 0;
 }
 
-// Bring the K-tiled copy up to `slots` rows (append-only between vec_gen bumps, as the
-// f16 copy).  Callers: every add before it publishes (rows [0, slots) written), and
-// exact searches (holding h->mu shared) for rows moved by a compaction / import /
-// load.  A reallocation happens only here, under ktile_mu, after a capacity growth
-// that drained every earlier search: a search reads the copy only after its own
-// ensure_ktile returned.
+// Bring the K-tiled copy up to `slots` rows.  Callers: every add before it publishes
+// (rows [0, slots) written), and exact searches (holding h->mu shared) for rows moved
+// by a compaction / import / load.  A reallocation happens only here, under ktile.mu,
+// after a capacity growth that drained every earlier search: a search reads the copy
+// only after its own ensure_ktile returned.
 static int ensure_ktile(vsg_index* h, size_t slots, hipStream_t s) {
-    std::lock_guard<std::mutex> g(h->ktile_mu);
+    RowCopy& c = h->ktile;
+    std::lock_guard<std::mutex> g(c.mu);
     // fault injection (tests only): the copy fails as a failed allocation would
     if (env_double("VSG_TEST_FAIL_KTILE", 0) != 0) return fail(VSG_ENOMEM, "K-tiled copy (injected failure)");
-    const size_t want_cap = (h->cap + KTILE_ROWS - 1) / KTILE_ROWS * KTILE_ROWS;
-    if (h->ktile_gen != h->vec_gen || h->ktile_cap < want_cap || h->ktile_rows > slots) {
-        if (h->ktile_cap < want_cap) {
-            h->fence.drain();
-            dev_free(h->d_ktile, s);
-            h->d_ktile = nullptr;
-            h->ktile_cap = 0;
-            HIP_TRY(dev_alloc(&h->d_ktile, want_cap * (h->row_bytes / 4), s));  // on the stream that fills it
+    const char* step = "hipStreamSynchronize(s)";
+    const hipError_t e = row_copy_ensure(
+        h, c, (h->cap + KTILE_ROWS - 1) / KTILE_ROWS * KTILE_ROWS, slots, s,
+        [&](size_t want_cap, hipStream_t s) {
+            row_copy_drop(h, c, s, h->d_ktile);
+            ROW_TRY(dev_alloc(&h->d_ktile, want_cap * (h->row_bytes / 4), s));
             // padding rows of the last tile are read (clamped loads never, but keep them defined)
-            HIP_TRY(hipMemsetAsync(h->d_ktile, 0, want_cap * h->row_bytes, s));
-            h->ktile_cap = want_cap;
-        }
-        h->ktile_rows = 0;
-        h->ktile_gen = h->vec_gen;
+            ROW_TRY(hipMemsetAsync(h->d_ktile, 0, want_cap * h->row_bytes, s));
+            return hipSuccess;
+        },
+        [](size_t, hipStream_t) { return hipSuccess; },  // nothing past the converted rows is read
+        [&](size_t, size_t slots, hipStream_t s) {       // from h->ktile.rows
+            ROW_TRY(launch_ktile_rows(reinterpret_cast<const float*>(h->d_vecs), (int)(h->row_bytes / 4), h->ktile.rows,
+                                      slots, h->d_ktile, s));
+            return hipSuccess;
+        });
+    return e == hipSuccess ? VSG_OK : row_copy_fail(step, e);
+}
+#undef ROW_TRY
+
+static_assert(PLAN_MFMA_BQ == MFMA_BQ && PLAN_MFMA_BR == MFMA_BR, "search_plan.hpp plans the tile the MFMA kernel runs");
+
+// One device search between ws_acquire and ws_release: the caller's arguments and the
+// carved-up workspace.
+extern "C++" struct SearchCall {
+    const float* q_dev;
+    size_t nq, k;
+    uint64_t* ok;
+    float* od;
+    uint32_t* oc;
+    hipStream_t s;
+    uint8_t* base;  // workspace block
+    SearchLayout at;
+    template <typename X>
+    X* region(size_t off) const {
+        return reinterpret_cast<X*>(base + off);
     }
-    if (h->ktile_rows < slots) {
-        HIP_TRY(launch_ktile_rows(reinterpret_cast<const float*>(h->d_vecs), (int)(h->row_bytes / 4), h->ktile_rows,
-                                  slots, h->d_ktile, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        h->ktile_rows = slots;
-    }
+};
+
+static int search_launch_rc(hipError_t err) {
+    if (err != hipSuccess) return fail(VSG_EDEVICE, std::string("search launch: ") + hipGetErrorString(err));
     return VSG_OK;
 }
 
+// Partial lists (plan.lists() per query, kin entries each; 0: k) -> the k best keys of
+// each query.  More than 64 lists were planned as whole 64-list groups: stage 1 merges
+// each group into one k-list behind the partial lists, stage 2 merges those.
+static hipError_t merge_parts_two_stage(float* pd, uint32_t* pi, const ExactPlan& plan, size_t nq, size_t k, int kin,
+                                        const uint64_t* keys, uint64_t* ok, float* od, uint32_t* oc, hipStream_t s) {
+    const int ng = plan.ngroups;
+    if (ng) {
+        MergeParams g1{};
+        g1.part_d = pd;
+        g1.part_i = pi;
+        g1.nq = (int)(nq * ng);
+        g1.parts = 64;
+        g1.k = (int)k;
+        g1.kin = kin;
+        g1.out_part_d = pd + plan.np_lists;
+        g1.out_part_i = pi + plan.np_lists;
+        const hipError_t err = launch_merge_parts(g1, s);
+        if (err != hipSuccess) return err;
+    }
+    MergeParams mp{};
+    mp.part_d = ng ? pd + plan.np_lists : pd;
+    mp.part_i = ng ? pi + plan.np_lists : pi;
+    mp.nq = (int)nq;
+    mp.parts = ng ? ng : plan.lists();
+    mp.k = (int)k;
+    mp.kin = ng ? 0 : kin;
+    mp.keys = keys;
+    mp.out_keys = ok;
+    mp.out_dist = od;
+    mp.out_counts = oc;
+    return launch_merge_parts(mp, s);
+}
+
+static int run_exact_mfma(vsg_index* h, const SearchCall& c, const ExactPlan& plan, size_t slots) {
+    float* pd = c.region<float>(c.at.part_d);
+    uint32_t* pi = c.region<uint32_t>(c.at.part_i);
+    MfmaExactParams mp{};
+    mp.vecs = reinterpret_cast<const float*>(h->d_vecs);
+    if (ktile_on(h)) {
+        const int rk = ensure_ktile(h, slots, c.s);
+        if (rk) return rk;
+        mp.ktile = h->d_ktile;
+    }
+    mp.sqnorm = h->d_sqnorm;
+    mp.queries = c.region<const float>(c.at.queries);
+    mp.qsqnorm = c.region<const float>(c.at.qnorms);
+    mp.row_floats = (int)(h->row_bytes / 4);
+    mp.nq = (int)c.nq;
+    mp.nslots = slots;
+    mp.flags = h->d_flags;
+    mp.qtiles = plan.qtiles;
+    mp.splits = (int)plan.splits;
+    mp.tiles_per_split = (int)plan.tiles_per_split;
+    mp.kmax = plan.kmax;
+    mp.bq = plan.bq;
+    mp.br = plan.br;
+    mp.part_d = pd;
+    mp.part_i = pi;
+    hipError_t err = launch_mfma_exact(h->mk, mp, c.s);
+    if (err == hipSuccess)
+        err = merge_parts_two_stage(pd, pi, plan, c.nq, c.k, plan.kmax, h->d_keys, c.ok, c.od, c.oc, c.s);
+    return search_launch_rc(err);
+}
+
+static int run_exact_valu(vsg_index* h, const SearchCall& c, const ExactPlan& plan, size_t slots) {
+    float* pd = c.region<float>(c.at.part_d);
+    uint32_t* pi = c.region<uint32_t>(c.at.part_i);
+    ExactParams ep{};
+    ep.vecs = h->d_vecs;
+    ep.row_bytes = h->row_bytes;
+    ep.nchunks = h->nchunks;
+    ep.queries = c.region<const uint8_t>(c.at.queries);
+    ep.nq = (int)c.nq;
+    ep.k = (int)c.k;
+    ep.nslots = slots;
+    ep.rows_per_block = std::max(plan.rows_per_block, 1);
+    ep.nblocks = plan.nblocks;
+    ep.flags = h->d_flags;
+    ep.part_d = pd;
+    ep.part_i = pi;
+    hipError_t err = slots > 0 ? launch_exact(h->st, h->mk, ep, c.s) : hipMemsetAsync(pi, 0xFF, plan.np * 4, c.s);
+    if (err == hipSuccess) err = merge_parts_two_stage(pd, pi, plan, c.nq, c.k, 0, h->d_keys, c.ok, c.od, c.oc, c.s);
+    return search_launch_rc(err);
+}
+
+// What a graph search was planned with beyond its layout.
+struct GraphPlan {
+    size_t ef;     // max(ef, k)
+    int upper_ef;  // VSG_SEARCH_UPPER_EF / vsg_index_set_upper_ef
+    bool rerank;   // f16 traversal: the beam of the f16 search is re-ranked in f32
+    bool filt;     // removed entries among the published slots
+    bool rerun;    // ... and room for the re-run lists of overflowing queries
+};
+
+// The f16-traversal leg: the f16 copy is searched with the f16 queries, the whole beam
+// (slots, not keys) goes to the f32 re-rank.
+static hipError_t run_graph_rerank(vsg_index* h, const SearchCall& c, SearchParams p) {
+    uint8_t* q16 = c.region<uint8_t>(c.at.q16);
+    uint64_t* ck = c.region<uint64_t>(c.at.cand_keys);
+    uint32_t* cc = c.region<uint32_t>(c.at.cand_counts);
+    hipError_t err = launch_prepare(ST_F16, c.q_dev, c.nq, h->dim, h->normalize, q16, h->row_bytes16, c.s);
+    p.g.vecs = h->d_vecs16;
+    p.g.row_bytes = h->row_bytes16;
+    p.g.nchunks = (int)(h->row_bytes16 / 16);
+    p.queries = q16;
+    p.k = p.ef;  // the whole beam goes to the re-rank
+    p.keys = nullptr;
+    p.out_keys = ck;
+    p.out_dist = c.region<float>(c.at.cand_dist);
+    p.out_counts = cc;
+    if (err == hipSuccess) err = launch_search(ST_F16, h->mk, p, c.s);
+    if (err != hipSuccess) return err;
+    RerankParams rp{};
+    rp.vecs = h->d_vecs;
+    rp.row_bytes = h->row_bytes;
+    rp.nchunks = h->nchunks;
+    rp.queries = c.region<const uint8_t>(c.at.queries);
+    rp.cand = ck;
+    rp.cand_counts = cc;
+    rp.nq = (int)c.nq;
+    rp.kc = p.ef;
+    rp.k = (int)c.k;
+    rp.keys = h->d_keys;
+    rp.out_keys = c.ok;
+    rp.out_dist = c.od;
+    rp.out_counts = c.oc;
+    return launch_rerank(h->mk, rp, c.s);
+}
+
+static int run_graph(vsg_index* h, const SearchCall& c, const GraphPlan& gp, size_t slots) {
+    SearchParams p{};
+    p.g = h->graph();
+    p.queries = c.region<const uint8_t>(c.at.queries);
+    p.nq = (int)c.nq;
+    p.k = (int)c.k;
+    p.ef = (int)gp.ef;
+    p.entry = h->pub_entry;
+    p.max_level = h->pub_max_level;
+    p.flags = h->d_flags;
+    p.keys = h->d_keys;
+    p.out_keys = c.ok;
+    p.out_dist = c.od;
+    p.out_counts = c.oc;
+    p.stats = h->d_stats;
+    p.xcd_map = env_double("VSG_SEARCH_XCD_MAP", 0) != 0 ? 1 : 0;
+    // candidate set in registers (hnsw_search_reg.hip, default: same results,
+    // +12-46% at ef >= 192, profiles/r01_search_phases.jsonl);
+    // VSG_SEARCH_REG=0 selects the LDS-list kernels
+    p.reg = env_double("VSG_SEARCH_REG", 1) != 0 ? 1 : 0;
+    p.hash_size = search_hash_size(p.ef, h->row_bytes, p.reg != 0, getenv("VSG_SEARCH_HASH_FACTOR"),
+                                   getenv("VSG_SEARCH_HASH_MIN"));
+    // waves per query: 1 = hnsw_search_kernel; 2 / 4 = cooperative kernel
+    // (large ef, where one wave is latency-bound on the list).  Same results;
+    // measured +5-7% at ef >= 321 (profiles/r01_search_waves.jsonl).
+    p.waves = (int)env_double("VSG_SEARCH_WAVES", p.ef >= 256 ? 2 : 1);
+    p.upper_ef = gp.upper_ef;
+    // persistent grid of resident waves (register kernel), for rows >= 1 KiB: C2
+    // (3 KiB rows, HBM-bound) +4-7 % (profiles/r05_persist.jsonl); a C4 shard
+    // (256 B rows, latency-bound) needs every resident wave: half of them cost
+    // 37 % at ef 192 and all of them gain nothing over the plain grid
+    // (r05_c4_persist.jsonl, r05_c4_pfrac.jsonl).  VSG_SEARCH_PERSIST=0 / 1 forces (the
+    // short-row kernels are compiled without the loop: hnsw_search_reg.hip persist_shape)
+    if (env_double("VSG_SEARCH_PERSIST", h->row_bytes >= 1024 ? 1 : 0) != 0) p.qnext = c.region<unsigned>(c.at.counter);
+    // removed entries among the published slots (tombstones, rolled-back
+    // adds): usearch's `allow` predicate -- traversed, never results
+    if (gp.filt) {
+        p.filt = 1;
+        p.removed_frac = (float)((double)(slots - h->live) / (double)slots);
+        if (gp.rerun) {
+            p.ovf = c.region<uint8_t>(c.at.overflow);
+            p.filt_lists = c.region<uint8_t>(c.at.rerun);
+            filt_rerun_shape(slots, &p.filt_cap, &p.filt_nlists);
+        }
+        // the re-run kernel (sorted list in device memory) descends greedily, so
+        // the filtered search does too: an overflowing query gets the same walk
+        // as one that did not; multi-entry descent applies to
+        // indexes without removed entries
+        p.upper_ef = 0;
+    }
+    // int8 sketch prefilter (same results, fewer f32 rows read): the register kernel,
+    // no removed entries
+    if (!gp.rerank && !gp.filt && p.reg && slots > 0 && prefilter_on(h, gp.ef, c.nq)) {
+        if (ensure_sketch(h, c.s)) {
+            p.sk = h->d_sketch;
+            p.sk_meta = h->d_sketch_meta;
+            p.sk_stride = sketch_stride(h->dim);
+            p.sk_dim = h->dim;
+        } else {
+            h->sketch_failures++;
+        }
+    }
+    return search_launch_rc(gp.rerank ? run_graph_rerank(h, c, p) : launch_search(h->st, h->mk, p, c.s));
+}
+
+// validate, plan, lay the workspace out, acquire it, prepare the queries, run one of
+// the three searches, release
 static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, size_t k, size_t ef,
                                 uint64_t* ok, float* od, uint32_t* oc, hipStream_t s, bool exact) {
     if (k == 0) return fail(VSG_EINVAL, "k must be >= 1 (Limit is NonZeroUsize)");
@@ -2261,297 +2515,51 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
     const size_t mfma_min = (size_t)env_double("VSG_EXACT_MFMA_MIN", 32);
     const bool use_mfma = exact && h->st == ST_F32 && k <= 16 && (h->row_bytes / 4) % 32 == 0 &&
                           nq >= mfma_min && h->pub_slots > 0 && env_double("VSG_EXACT_MFMA", 1) != 0;
-    // plan: partial-list shapes, then one scratch block for everything
     const size_t slots = h->pub_slots;  // rows of the last completed add
-    int qtiles = 0, kmax = 0, nparts = 0, nblocks = 1, rpb = 1, ngroups = 0;
-    size_t splits = 0, tps = 0, np = 0, np_lists = 0;
-    const int bq = nq <= 64 ? 64 : MFMA_BQ;  // the 64-query tile for small batches
-    const int br = bq == 64 ? 256 : MFMA_BR;  // ... 256 rows deep
-    if (use_mfma) {
-        qtiles = (int)((nq + bq - 1) / bq);
-        const size_t ntiles = (slots + br - 1) / br;
-        // (query tile, row split) blocks in whole rounds of resident blocks (2 per CU:
-        // 64 / 80 KiB of LDS): 1,024 = two rounds of the 128 x 128 tile, 512 = one of
-        // the 256 x 64 tile (round 2: 1,024 blocks of a 128 x 64 tile, 1.33 rounds)
-        const size_t target = bq == 64 ? 512 : 1024;
-        splits = std::min<size_t>(ntiles, std::max<size_t>(1, (target + qtiles - 1) / qtiles));
-        tps = (ntiles + splits - 1) / splits;
-        splits = (ntiles + tps - 1) / tps;
-        kmax = 16;
-        // more than 64 partial lists per query: whole 64-list groups (padding splits
-        // hold no rows and write empty lists), merged in two stages
-        const size_t lists = (size_t)(br / 64) * 2;  // per split: row waves x half-waves
-        if (splits * lists > 64) {
-            splits = (splits * lists + 63) / 64 * 64 / lists;
-            ngroups = (int)(splits * lists / 64);
-        }
-        nparts = (int)(splits * lists);
-        np_lists = nq * (size_t)nparts * kmax;
-        np = np_lists + (ngroups ? nq * (size_t)ngroups * k : 0);
-    } else if (exact) {
-        // grid.y = row blocks (<= 65535 per dimension).  4,096-row blocks fill the
-        // chip from ~32 queries on; a smaller batch gets more, shorter blocks so
-        // the launch still holds >= VSG_EXACT_MIN_WAVES waves (at one query the
-        // 245 waves of 4,096-row blocks read C5's 6 GB at 0.11 of HBM,
-        // profiles/r03_bench_c5_batches.jsonl), down to 64 rows per block
-        const size_t want = (size_t)env_double("VSG_EXACT_MIN_WAVES", 8192);
-        size_t nb = std::max<size_t>((slots + 4095) / 4096, std::min((want + nq - 1) / nq, (slots + 63) / 64));
-        nblocks = (int)std::min<size_t>(32768, std::max<size_t>(1, nb));
-        // large k: bound the partial lists (nq x nblocks x k x 8 B) to ~1 GiB
-        const size_t cap_blocks = std::max<size_t>(1, ((size_t)1 << 30) / (8 * nq * k));
-        nblocks = (int)std::min<size_t>((size_t)nblocks, cap_blocks);
-        // more than 64 lists per query: merged in two stages (64-list groups in
-        // parallel, then the group results), not by one wave walking all of them
-        if (nblocks > 64 && slots > 0) {
-            nblocks = (nblocks + 63) / 64 * 64;  // padding blocks hold no rows (empty lists)
-            ngroups = nblocks / 64;
-        }
-        rpb = (int)((slots + nblocks - 1) / nblocks);
-        if (slots == 0) nblocks = 1;
-        np_lists = nq * (size_t)nblocks * k;
-        np = np_lists + (ngroups ? nq * (size_t)ngroups * k : 0);
-    }
-    // f16 traversal: the beam (ef slots) of the f16 search is re-ranked in f32
-    const bool rerank = !exact && h->f16_trav && slots > 0;
-    const size_t efr = ef_eff;
-    size_t rr_b = 0;
-    if (rerank) {
-        int rc0 = ensure_shadow(h, s);
+    ExactPlan plan;
+    if (use_mfma)
+        plan = plan_exact_mfma(nq, slots, k);
+    else if (exact)
+        plan = plan_exact_valu(nq, slots, k, (size_t)env_double("VSG_EXACT_MIN_WAVES", 8192));
+    GraphPlan gp{ef_eff, upper_ef, false, false, false};
+    SearchLayout::Sizes sz;
+    sz.queries = nq * h->row_bytes;
+    if (use_mfma) sz.qnorms = nq * 4;
+    sz.part = plan.np * 4;
+    gp.rerank = !exact && h->f16_trav && slots > 0;
+    if (gp.rerank) {
+        const int rc0 = ensure_shadow(h, s);
         if (rc0) return rc0;
-        // f16 queries | candidate slots | candidate distances | candidate counts
-        rr_b = align256(nq * h->row_bytes16) + align256(nq * efr * 8) + 2 * align256(nq * efr * 4);
+        sz.q16 = nq * h->row_bytes16;
+        sz.cand_keys = nq * ef_eff * 8;
+        sz.cand_dist = sz.cand_counts = nq * ef_eff * 4;
     }
-    const size_t qp_b = align256(nq * h->row_bytes), qsq_b = use_mfma ? align256(nq * 4) : 0,
-                 part_b = align256(np * 4);
     // removed entries among the published slots: the filtered search, whose
     // overflowing queries are re-run on device-memory lists (per-query flags +
     // the lists, hnsw_search_filt.hip)
-    const bool filt = !exact && slots > h->live;
-    bool rerun = filt && env_double("VSG_SEARCH_FILT_RERUN", 1) != 0;  // 0: degrade instead (probes)
-    size_t filt_b = filt ? align256(nq) + (rerun ? align256(filt_rerun_bytes(slots)) : 0) : 0;
+    gp.filt = !exact && slots > h->live;
+    gp.rerun = gp.filt && env_double("VSG_SEARCH_FILT_RERUN", 1) != 0;  // 0: degrade instead (probes)
+    if (gp.filt) sz.overflow = nq;
+    if (gp.rerun) sz.rerun = filt_rerun_bytes(slots);
+    SearchCall c{q_dev, nq, k, ok, od, oc, s, nullptr, SearchLayout(sz)};
     Workspace* ws = nullptr;
-    int rc = ws_acquire(h, qp_b + qsq_b + 2 * part_b + rr_b + filt_b + 256, s, &ws);
-    if (rc && rerun) {
+    int rc = ws_acquire(h, c.at.total, s, &ws);
+    if (rc && gp.rerun) {
         // no room for the re-run lists: the degraded, counted filtered search
         // (search_filter_overflow) rather than a failed one
-        rerun = false;
-        filt_b = align256(nq);
-        rc = ws_acquire(h, qp_b + qsq_b + 2 * part_b + rr_b + filt_b + 256, s, &ws);
+        gp.rerun = false;
+        sz.rerun = 0;
+        c.at = SearchLayout(sz);
+        rc = ws_acquire(h, c.at.total, s, &ws);
     }
     if (rc) return rc;
-    uint8_t* fb = ws->base + qp_b + qsq_b + 2 * part_b + rr_b;
-    unsigned* qnext = reinterpret_cast<unsigned*>(fb + filt_b);  // persistent-grid counter (probes)
-    uint8_t* rr = ws->base + qp_b + qsq_b + 2 * part_b;
-    uint8_t* q16 = rr;
-    uint64_t* ck = reinterpret_cast<uint64_t*>(q16 + align256(nq * h->row_bytes16));
-    float* cd = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(ck) + align256(nq * efr * 8));
-    uint32_t* cc = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(cd) + align256(nq * efr * 4));
-    uint8_t* qp = ws->base;
-    float* qsq = qsq_b ? reinterpret_cast<float*>(ws->base + qp_b) : nullptr;
-    float* pd = reinterpret_cast<float*>(ws->base + qp_b + qsq_b);
-    uint32_t* pi = reinterpret_cast<uint32_t*>(ws->base + qp_b + qsq_b + part_b);
-    hipError_t err = launch_prepare(h->st, q_dev, nq, h->dim, h->normalize, qp, h->row_bytes, s, qsq);
-    if (err == hipSuccess && use_mfma) {
-        MfmaExactParams mp{};
-        mp.vecs = reinterpret_cast<const float*>(h->d_vecs);
-        if (ktile_on(h)) {
-            const int rk = ensure_ktile(h, slots, s);
-            if (rk) {
-                ws_release(h, ws, s);
-                return rk;
-            }
-            mp.ktile = h->d_ktile;
-        }
-        mp.sqnorm = h->d_sqnorm;
-        mp.queries = reinterpret_cast<const float*>(qp);
-        mp.qsqnorm = qsq;
-        mp.row_floats = (int)(h->row_bytes / 4);
-        mp.nq = (int)nq;
-        mp.nslots = slots;
-        mp.flags = h->d_flags;
-        mp.qtiles = qtiles;
-        mp.splits = (int)splits;
-        mp.tiles_per_split = (int)tps;
-        mp.kmax = kmax;
-        mp.bq = bq;
-        mp.br = br;
-        mp.part_d = pd;
-        mp.part_i = pi;
-        err = launch_mfma_exact(h->mk, mp, s);
-        if (err == hipSuccess && ngroups) {  // stage 1: each 64-list group -> one k-list
-            MergeParams g1{};
-            g1.part_d = pd;
-            g1.part_i = pi;
-            g1.nq = (int)(nq * ngroups);
-            g1.parts = 64;
-            g1.k = (int)k;
-            g1.kin = kmax;
-            g1.out_part_d = pd + np_lists;
-            g1.out_part_i = pi + np_lists;
-            err = launch_merge_parts(g1, s);
-        }
-        if (err == hipSuccess) {
-            MergeParams gp{};
-            gp.part_d = ngroups ? pd + np_lists : pd;
-            gp.part_i = ngroups ? pi + np_lists : pi;
-            gp.nq = (int)nq;
-            gp.parts = ngroups ? ngroups : nparts;
-            gp.k = (int)k;
-            gp.kin = ngroups ? 0 : kmax;
-            gp.keys = h->d_keys;
-            gp.out_keys = ok;
-            gp.out_dist = od;
-            gp.out_counts = oc;
-            err = launch_merge_parts(gp, s);
-        }
-    } else if (err == hipSuccess && !exact) {
-        const size_t e = ef_eff;
-        SearchParams p{};
-        p.g = h->graph();
-        p.queries = qp;
-        p.nq = (int)nq;
-        p.k = (int)k;
-        p.ef = (int)e;
-        p.entry = h->pub_entry;
-        p.max_level = h->pub_max_level;
-        p.flags = h->d_flags;
-        p.keys = h->d_keys;
-        p.out_keys = ok;
-        p.out_dist = od;
-        p.out_counts = oc;
-        p.stats = h->d_stats;
-        p.xcd_map = env_double("VSG_SEARCH_XCD_MAP", 0) != 0 ? 1 : 0;
-        {
-            // visited table: LDS is the occupancy limit at large ef, and a
-            // forgotten node costs one more row read -- cheap for short rows
-            const bool wide = h->row_bytes >= 1024;
-            const bool reg = env_double("VSG_SEARCH_REG", 1) != 0;
-            // register kernel: sweep in profiles/r01_search_hash_reg.jsonl
-            const int factor = (int)env_double("VSG_SEARCH_HASH_FACTOR", wide ? (reg ? 8 : 12) : (reg ? 4 : 6));
-            // VSG_SEARCH_HASH_MIN (probes): smallest table (entries, multiple of 64)
-            const int hmin = std::max(64, (int)env_double("VSG_SEARCH_HASH_MIN", wide ? 2048 : 1024)) & ~63;
-            const int raw = std::min(16384, (int)(((long)factor * p.ef + 63) & ~63L));
-            p.hash_size = std::max(raw, hmin);
-        }
-        // waves per query: 1 = hnsw_search_kernel; 2 / 4 = cooperative kernel
-        // (large ef, where one wave is latency-bound on the list).  Same results;
-        // measured +5-7% at ef >= 321 (profiles/r01_search_waves.jsonl).
-        p.waves = (int)env_double("VSG_SEARCH_WAVES", p.ef >= 256 ? 2 : 1);
-        // candidate set in registers (hnsw_search_reg.hip, default: same results,
-        // +12-46% at ef >= 192, profiles/r01_search_phases.jsonl);
-        // VSG_SEARCH_REG=0 selects the LDS-list kernels
-        p.reg = env_double("VSG_SEARCH_REG", 1) != 0 ? 1 : 0;
-        p.upper_ef = upper_ef;
-        // persistent grid of resident waves (register kernel), for rows >= 1 KiB: C2
-        // (3 KiB rows, HBM-bound) +4-7 % (profiles/r05_persist.jsonl); a C4 shard
-        // (256 B rows, latency-bound) needs every resident wave: half of them cost
-        // 37 % at ef 192 and all of them gain nothing over the plain grid
-        // (r05_c4_persist.jsonl, r05_c4_pfrac.jsonl).  VSG_SEARCH_PERSIST=0 / 1 forces (the
-        // short-row kernels are compiled without the loop: hnsw_search_reg.hip persist_shape)
-        if (env_double("VSG_SEARCH_PERSIST", h->row_bytes >= 1024 ? 1 : 0) != 0) p.qnext = qnext;
-        // removed entries among the published slots (tombstones, rolled-back
-        // adds): usearch's `allow` predicate -- traversed, never results
-        if (filt) {
-            p.filt = 1;
-            p.removed_frac = (float)((double)(slots - h->live) / (double)slots);
-            if (rerun) {
-                p.ovf = fb;
-                p.filt_lists = fb + align256(nq);
-                filt_rerun_shape(slots, &p.filt_cap, &p.filt_nlists);
-            }
-            // the re-run kernel (sorted list in device memory) descends greedily, so
-            // the filtered search does too: an overflowing query gets the same walk
-            // as one that did not; multi-entry descent applies to
-            // indexes without removed entries
-            p.upper_ef = 0;
-        }
-        // int8 sketch prefilter (same results, fewer f32 rows read): the register kernel,
-        // no removed entries
-        if (!rerank && !filt && p.reg && slots > 0 && prefilter_on(h, e, nq)) {
-            if (ensure_sketch(h, s)) {
-                p.sk = h->d_sketch;
-                p.sk_meta = h->d_sketch_meta;
-                p.sk_stride = sketch_stride(h->dim);
-                p.sk_dim = h->dim;
-            } else {
-                h->sketch_failures++;
-            }
-        }
-        if (!rerank) {
-            err = launch_search(h->st, h->mk, p, s);
-        } else {
-            err = launch_prepare(ST_F16, q_dev, nq, h->dim, h->normalize, q16, h->row_bytes16, s);
-            p.g.vecs = h->d_vecs16;
-            p.g.row_bytes = h->row_bytes16;
-            p.g.nchunks = (int)(h->row_bytes16 / 16);
-            p.queries = q16;
-            p.k = (int)e;  // the whole beam goes to the re-rank
-            p.keys = nullptr;
-            p.out_keys = ck;
-            p.out_dist = cd;
-            p.out_counts = cc;
-            if (err == hipSuccess) err = launch_search(ST_F16, h->mk, p, s);
-            if (err == hipSuccess) {
-                RerankParams rp{};
-                rp.vecs = h->d_vecs;
-                rp.row_bytes = h->row_bytes;
-                rp.nchunks = h->nchunks;
-                rp.queries = qp;
-                rp.cand = ck;
-                rp.cand_counts = cc;
-                rp.nq = (int)nq;
-                rp.kc = (int)e;
-                rp.k = (int)k;
-                rp.keys = h->d_keys;
-                rp.out_keys = ok;
-                rp.out_dist = od;
-                rp.out_counts = oc;
-                err = launch_rerank(h->mk, rp, s);
-            }
-        }
-    } else if (err == hipSuccess) {
-        ExactParams ep{};
-        ep.vecs = h->d_vecs;
-        ep.row_bytes = h->row_bytes;
-        ep.nchunks = h->nchunks;
-        ep.queries = qp;
-        ep.nq = (int)nq;
-        ep.k = (int)k;
-        ep.nslots = slots;
-        ep.rows_per_block = std::max(rpb, 1);
-        ep.nblocks = nblocks;
-        ep.flags = h->d_flags;
-        ep.part_d = pd;
-        ep.part_i = pi;
-        err = slots > 0 ? launch_exact(h->st, h->mk, ep, s) : hipMemsetAsync(pi, 0xFF, np * 4, s);
-        if (err == hipSuccess && ngroups) {  // stage 1: each 64-list group -> one list
-            MergeParams g1{};
-            g1.part_d = pd;
-            g1.part_i = pi;
-            g1.nq = (int)(nq * ngroups);
-            g1.parts = 64;
-            g1.k = (int)k;
-            g1.out_part_d = pd + np_lists;
-            g1.out_part_i = pi + np_lists;
-            err = launch_merge_parts(g1, s);
-        }
-        if (err == hipSuccess) {
-            MergeParams mp{};
-            mp.part_d = ngroups ? pd + np_lists : pd;
-            mp.part_i = ngroups ? pi + np_lists : pi;
-            mp.nq = (int)nq;
-            mp.parts = ngroups ? ngroups : nblocks;
-            mp.k = (int)k;
-            mp.keys = h->d_keys;
-            mp.out_keys = ok;
-            mp.out_dist = od;
-            mp.out_counts = oc;
-            err = launch_merge_parts(mp, s);
-        }
-    }
+    c.base = ws->base;
+    rc = search_launch_rc(launch_prepare(h->st, q_dev, nq, h->dim, h->normalize, c.base + c.at.queries, h->row_bytes, s,
+                                         use_mfma ? c.region<float>(c.at.qnorms) : nullptr));
+    if (rc == VSG_OK)
+        rc = use_mfma ? run_exact_mfma(h, c, plan, slots) : exact ? run_exact_valu(h, c, plan, slots) : run_graph(h, c, gp, slots);
     ws_release(h, ws, s);
-    if (err != hipSuccess) return fail(VSG_EDEVICE, std::string("search launch: ") + hipGetErrorString(err));
-    return VSG_OK;
+    return rc;
 }
 
 static SearchCtx* ctx_acquire(vsg_index* h) {
@@ -2847,17 +2855,9 @@ int vsg_index_set_prefilter(vsg_index_t* h, int on) {
     if (!h) return fail(VSG_EINVAL, "null index");
     std::unique_lock<std::shared_mutex> lk(h->mu);
     DeviceGuard dg(h->device);
-    std::lock_guard<std::mutex> g(h->sketch_mu);
+    std::lock_guard<std::mutex> g(h->sketch.mu);
     h->prefilter = on != 0;
-    if (!on && h->d_sketch) {
-        h->fence.drain();  // device searches enqueued earlier may still read the rows
-        dev_free(h->d_sketch, h->stream);
-        dev_free(h->d_sketch_meta, h->stream);
-        h->d_sketch = nullptr;
-        h->d_sketch_meta = nullptr;
-        h->sketch_cap = h->sketch_rows = 0;
-        h->sketch_gen = ~0ull;
-    }
+    if (!on && h->d_sketch) row_copy_drop(h, h->sketch, h->stream, h->d_sketch, h->d_sketch_meta);
     return VSG_OK;
 }
 
@@ -2868,16 +2868,11 @@ int vsg_index_set_f16_traversal(vsg_index_t* h, int enable) {
     if (enable && h->st != ST_F32) return fail(VSG_EINVAL, "f16 traversal needs f32 storage");
     if (enable && (h->opt.flags & VSG_FLAG_EXACT_ONLY)) return fail(VSG_EUNSUPPORTED, "exact-only index");
     DeviceGuard dg(h->device);
-    std::lock_guard<std::mutex> g(h->shadow_mu);
+    std::lock_guard<std::mutex> g(h->shadow.mu);
     h->f16_trav = enable != 0;
     h->opt.flags = enable ? (h->opt.flags | VSG_FLAG_F16_TRAVERSAL) : (h->opt.flags & ~VSG_FLAG_F16_TRAVERSAL);
-    if (!enable && h->d_vecs16) {
-        h->fence.drain();  // device searches enqueued earlier may still walk the copy (mu held:
-        dev_free(h->d_vecs16, h->stream);  // no host search is in flight)
-        h->d_vecs16 = nullptr;
-        h->shadow_cap = h->shadow_rows = 0;
-        h->shadow_gen = ~0ull;
-    }
+    // mu held exclusively: no host search is in flight
+    if (!enable && h->d_vecs16) row_copy_drop(h, h->shadow, h->stream, h->d_vecs16);
     return VSG_OK;
 }
 
