@@ -223,7 +223,8 @@ int vsg_index_set_f16_traversal(vsg_index_t* index, int enable);
  * cos / ip, rows of 1 to 8 KiB, ef <= 448, an index without removed entries, f16
  * traversal off; every other search runs as before.  Until this is called the
  * environment variable VSG_SEARCH_PREFILTER (0 / 1) decides, and when that is unset the
- * prefilter runs where it measured faster: ef <= 64 and batches of >= 4096 queries.
+ * prefilter runs where it measured faster: ef <= 64 and batches of >= 4096 queries, or
+ * ef <= 192 and batches of >= 10000 queries.
  * If the sketch cannot be allocated the search runs unfiltered and succeeds. */
 int vsg_index_set_prefilter(vsg_index_t* index, int on);
 

@@ -14,6 +14,10 @@ namespace vsg {
 #ifndef VSG_COMPACT_EARLY
 #define VSG_COMPACT_EARLY 0
 #endif
+// the prefiltered beam computes bound_ef() under the adjacency load (0: after it; probes)
+#ifndef VSG_TAU_EARLY
+#define VSG_TAU_EARLY 1
+#endif
 
 // (distance, slot) -> key whose unsigned order is cand_less order (-0 == +0).
 __device__ __forceinline__ uint64_t cand_key(float d, uint32_t id) {
@@ -334,7 +338,8 @@ __device__ __forceinline__ void admit(RegSet<R>& B, bool mine, uint64_t ck, bool
 // counts in ndist.  For the bound to bite before the first compaction, tkey is
 // also lowered once per expansion to bound_ef(), an upper bound of the ef-th
 // smallest key of B: B is a superset of top_ef(S), so that key is the reference's
-// "worst of a full list", at or above which nothing is ever admitted.
+// "worst of a full list", at or above which nothing is ever admitted.  The select runs
+// between the issue of the expansion's adjacency load and the first use of its result.
 // PRE (hnsw_search_reg.hip: SketchPre, sketch_device.hpp) provides
 //   int filter(WaveLds& w, int cnt, uint64_t tkey)
 // which drops from w.todo[0..cnt) the ids it can reject and returns the survivors' count.
@@ -409,6 +414,16 @@ __device__ __forceinline__ void beam_reg(const GraphDev& g, const QReg<G, VM, T>
         // batch (B only ever keeps the best ef of everything evaluated)
         for (int c0 = 0; c0 < m; c0 += 64) {
             const uint32_t nb = c0 + lane < m ? row[c0 + lane] : VSG_EMPTY;
+            if constexpr (!std::is_same<PRE, NoSketch>::value) {
+                // the first piece's bound_ef() under the adjacency round trip: B is final
+                // since the last admit, and nb is not used before the select is done (a
+                // later piece recomputes it below, B having changed)
+                if (VSG_TAU_EARLY && c0 == 0 && B.size >= ef && B.size != tau_size) {
+                    const uint64_t tau = B.bound_ef(ef);
+                    if (tau < B.tkey) B.tkey = tau;
+                    tau_size = B.size;
+                }
+            }
             const bool full = __ballot(nb != VSG_EMPTY) == ~0ull;
 #ifdef VSG_SEARCH_PROFILE
             {

@@ -63,7 +63,7 @@ __device__ __forceinline__ void search_reg_one(const SearchParams& p, int qi, ui
         float dcur = dist_one<G, VM, U, T, MET>(g, q, cur, w);
         ++ndist;
         RegSet<R> B;
-        using SS = SketchShape<G, VM>;
+        using SS = SketchShape<G, VM, U>;
         using Pre = std::conditional_t<PF, SketchPre<SS::GS, SS::VMS, SS::US>, NoSketch>;
         Pre pre_s;
         Pre* pre = nullptr;
@@ -219,6 +219,11 @@ bool search_prefilter_supported(Storage st, MetricKind mk, int nchunks, int ef) 
 
 size_t search_reg_lds_bytes(int hash) { return wave_lds_bytes(hash, 0, 0); }
 
+// persistent-grid fraction of the prefilter instances (launch_search_reg)
+#ifndef VSG_PERSIST_FRAC_PF
+#define VSG_PERSIST_FRAC_PF 1.0
+#endif
+
 static double env_frac(const char* name, double dflt) {
     const char* e = getenv(name);
     return e ? atof(e) : dflt;
@@ -262,7 +267,7 @@ hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, h
             constexpr int G = decltype(sh)::G, VM = decltype(sh)::VM, U = decltype(sh)::U;
             using T = typename decltype(tt)::T;
             constexpr int MET = decltype(mt)::MET;
-            auto run = [&](auto kern, size_t lds) {
+            auto run = [&](auto kern, size_t lds, bool pf = false) {
                 if (lds > 65536)
                     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 constexpr int CH = 1 << 22;  // 64 work-items each: the AQL grid size is 32-bit
@@ -282,7 +287,12 @@ hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, h
                         // waves/SIMD) 0.35-0.6 were level at 3.34 M (r05_pfrac.jsonl);
                         // VSG_SEARCH_PERSIST_FRAC overrides (probes)
                         static const double frac = std::min(1.0, std::max(0.05, env_frac("VSG_SEARCH_PERSIST_FRAC", 0.75)));
-                        const int res = std::max(1, (int)(frac * resident_blocks((const void*)kern, lds)));
+                        // the prefilter instances are bound by each wave's chain of dependent gathers,
+                        // not by bytes, so every resident wave helps: C2 kernel ms at fractions 0.5 /
+                        // 0.75 / 0.9 / 1.0: 2.95 / 2.36 / 2.26 / 2.21 (profiles/prefilter_i8_gate.jsonl)
+                        static const double frac_pf =
+                            std::min(1.0, std::max(0.05, env_frac("VSG_SEARCH_PERSIST_FRAC", VSG_PERSIST_FRAC_PF)));
+                        const int res = std::max(1, (int)((pf ? frac_pf : frac) * resident_blocks((const void*)kern, lds)));
                         grid = (unsigned)std::max(1, std::min(c.nq, res));
                         err = hipMemsetAsync(p.qnext, 0, sizeof(unsigned), s);
                         if (err != hipSuccess) break;
@@ -294,7 +304,9 @@ hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, h
             // the sketch prefilter: f32 dot-metric rows of >= 1 KiB, 2 / 4 / 8 register rows
             if constexpr (prefilter_shape<G, VM, T, MET, R>()) {
                 if (p.sk) {
-                    run(hnsw_search_reg_kernel<G, VM, U, T, MET, R, true>, lds_plain + SketchShape<G, VM>::LDS_BYTES);
+                    constexpr int UP = prefilter_u<G, VM, U>();
+                    run(hnsw_search_reg_kernel<G, VM, UP, T, MET, R, true>, lds_plain + SketchShape<G, VM, UP>::LDS_BYTES,
+                        true);
                     return;
                 }
             }

@@ -15,19 +15,46 @@
 // without FMA: |fl(sum a_i b_i) - sum a_i b_i| <= g_d sum |a_i b_i|,
 // g_d = d u / (1 - d u)):
 //   exact sum   fl(q.x): error <= g_d sum |q_i x_i| <= g_d |q| |x|;
-//   sketch sum  s = fl(sum q_i u_i), u_i <= 255: error <= g_d 255 |q|_1
-//               <= g_d 255 sqrt(d) |q|;
-//   bias        128 fl(sum q_i): error <= 128 g_d sqrt(d) |q|;
-//   t = fl(s - 128 sum q), fl(scale t), the FMA with |q| err: three roundings
-//               of values bounded by |q| (|x| + 2 err) (|scale t| ~ |q.x~|).
-// Divided by |q| and rounded up generously (d + 8 for d, 384 for 255 + 128,
-// 1.01 for the 1 / (1 - d u) factors; |x| <= sqrt(d) max|x_i| = 127 sqrt(d) scale):
+//   sketch side: budgeted as g_d 384 sqrt(d) |q| scale plus three roundings of values
+//               bounded by |q| (|x| + 2 err) -- the f32 sums of the first kernel
+//               (fl(sum q_i u_i) and its bias 128 fl(sum q_i)); the integer sketch pass
+//               below spends less.
+// Divided by |q| and rounded up generously (d + 8 for d, 1.01 for the 1 / (1 - d u)
+// factors; |x| <= sqrt(d) max|x_i| = 127 sqrt(d) scale):
 //     slack = (d + 8) u 1.01 * (384 sqrt(d) scale + |x|_up + 2 e) + 4 u (|x|_up + 2 e),
 // of the order of dim 2^-24 (|x| + 384 sqrt(dim) scale): 3e-4 for a unit 768-d
 // row against e ~ 8e-3.  e itself is a f32 sum of squares of residuals each
 // computed with one rounding (FMA), so it is inflated by (1 + (d + 8) 2^-23)
 // before the slack is added.  The kernel multiplies err by an upper bound of
 // |q| (its f32 norm inflated the same way).
+//
+// The sketch pass itself is integer (sketch_device.hpp).  Per search the query is
+// quantised to 16 bits, q16_i = rint(q_i / s_q), s_q = max|q_i| / 32512, held as two
+// signed int8 planes q16 = 256 h + l (h in [-127, 127], l in [-128, 127]); a row's signed
+// bytes are x'_i = u_i - 128 (u ^ 0x80).  With q^ = s_q q16 (real numbers),
+//     q.x = q^.x~ + (q - q^).x~ + q.(x - x~),
+//     q^.x~ = s_q scale (256 H + L),  H = sum x'_i h_i,  L = sum x'_i l_i,
+// H and L exact in int32 (|H|, |L| <= 127 128 d < 2^31 up to 8 KiB rows and far beyond),
+//     |(q - q^).x~| <= qerr |x~| <= qerr 127 sqrt(d) scale,  qerr >= |q - q^|_2,
+//     |q.(x - x~)| <= |q| e.
+// The kernel evaluates (sketch_upper)
+//     ub = fma(p, S, fma(qe, scale, fl(qn err))),  p = fl(s_q scale),
+//     S = fma(256, fl(H), fl(L)),  qe = qerr 127 sqrt(d) 1.001.
+// Its roundings: fl(H), fl(L) (inexact only above 2^24, d > 1040) and S's fma, each
+// relative u of at most 256 |H| + |L| <= sum |x'_i| (|q16_i| + 256)
+// <= 127 sqrt(d) (|q16| + 256 sqrt(d)); times p, and s_q 256 sqrt(d) <= |q| sqrt(d) / 127:
+//     p |S - (256 H + L)| <= 3.03 u (1 + sqrt(d) / 127) 127 sqrt(d) scale |q|
+//                         <= (385 + 3.1 sqrt(d)) u sqrt(d) scale |q|,
+// below the (d + 8) u 1.01 * 384 sqrt(d) scale |q| that err holds for the f32 sketch sums
+// (388 (d + 8) > 385 + 3.1 sqrt(d) for every d).  p, fl(qn err) and the two fmas are four
+// roundings: of |p S| <= |q| (|x| + e) twice, of qn err three times (err < 0.52 (|x|_up +
+// 2 e): e <= (|x|_up + 2 e) / 2, slack < 0.02 of it), of qe scale twice -- 3.7 u |q| (|x|_up
+// + 2 e), inside err's 4 u (|x|_up + 2 e), and the 2 u qe scale inside qe's factor 1.001.
+// So no row's err is loosened; the query pays qe scale, 1-2e-4 for a unit 768-d query
+// against |q| err ~ 8e-3.  Underflow: the query is filtered only for max|q_i| in
+// [2^-40, 2^40] and a row rejected only for p >= 2^-80, where p, p S and qn err are
+// normal floats; qe scale >= 0 can only lose 2^-149 to it, and qerr carries 2^-40 max|q_i|
+// for the squares of residuals that underflowed.
 //
 // err = +inf (never rejected) for a row with a non-finite element, an all-zero
 // row, a scale that is not a normal float or whose reciprocal overflows.
@@ -123,6 +150,65 @@ static inline VSG_HD SketchMeta sketch_row(const float* x, int dim, uint8_t* out
 // upper bound of |q|_2 from the f32 sum of squares
 static inline VSG_HD float sketch_qnorm_up(float sum_q2, int dim) {
     return sqrtf(sum_q2) * (1.f + (float)(dim + 8) * 1.1920929e-7f);
+}
+
+// ---- the query side: 16-bit quantisation in two signed int8 planes ----
+
+// s_q of a query with that max |q_i|; 0 = the query runs unfiltered (all-zero,
+// non-finite, or outside [2^-40, 2^40]: inside, s_q, 1 / s_q and |q| are normal floats
+// far from both ends of the range)
+static inline VSG_HD float sketch_qscale(float maxabs) {
+    if (!(maxabs >= 9.094947e-13f) || !(maxabs <= 1.0995116e12f)) return 0.f;
+    return maxabs / 32512.f;
+}
+
+// q16 = rint(q / s_q), |q16| <= 32512
+static inline VSG_HD int sketch_q16(float q, float sq) {
+    float k = rintf(q / sq);
+    k = k > 32512.f ? 32512.f : (k < -32512.f ? -32512.f : k);
+    return (int)k;
+}
+// q16 = 256 h + l: h = floor((q16 + 128) / 256) in [-127, 127], l in [-128, 127]
+static inline VSG_HD int sketch_q16_hi(int q16) { return (q16 + 32768 + 128) / 256 - 128; }
+static inline VSG_HD int sketch_q16_lo(int q16) { return q16 - 256 * sketch_q16_hi(q16); }
+
+// squared residual of one element: (q - s_q q16)^2, the residual with one rounding
+static inline VSG_HD float sketch_qres2(float q, float sq, int q16) {
+    const float r = fmaf(-sq, (float)q16, q);
+    return r * r;
+}
+
+// What a search keeps of its query: sq = s_q (0 = no filter), qe = the query's share of the
+// bound per unit of a row's scale (qerr 127 sqrt(d), rounded up), qn >= |q|.
+struct SketchQuery {
+    float sq, qe, qn;
+};
+
+// from max |q_i| and the f32 sums sum_res2 = sum (q_i - s_q q16_i)^2 and sum_q2 = sum q_i^2
+// (any order)
+static inline VSG_HD SketchQuery sketch_query(float maxabs, float sum_res2, float sum_q2, int dim) {
+    SketchQuery r;
+    r.sq = sketch_qscale(maxabs);
+    r.qn = sketch_qnorm_up(sum_q2, dim);
+    const float infl = 1.f + (float)(dim + 8) * 1.1920929e-7f;
+    // + 2^-40 max|q|: above anything the squares lost to underflow
+    const float qerr = sqrtf(sum_res2) * infl + 9.094947e-13f * maxabs;
+    r.qe = qerr * (127.f * sqrtf((float)dim)) * 1.001f;
+    if (!(r.qe < INFINITY) || !(r.qn < INFINITY)) r.sq = 0.f;
+    return r;
+}
+
+// smallest s_q * scale a row is rejected on (2^-80): the product p and p S are normal
+// floats above it, and qn err >= 2^11 p
+#define VSG_SKETCH_PMIN 8.2718061e-25f
+
+// The upper bound of q . x in the kernel's own f32 arithmetic, from the integer sums
+// H = sum x'_i h_i and L = sum x'_i l_i (x' = u - 128).  +inf / NaN: not rejected.
+static inline VSG_HD float sketch_upper(const SketchQuery& q, SketchMeta m, int H, int L) {
+    const float p = q.sq * m.scale;
+    const float S = fmaf(256.f, (float)H, (float)L);
+    const float ub = fmaf(p, S, fmaf(q.qe, m.scale, q.qn * m.err));
+    return p >= VSG_SKETCH_PMIN ? ub : INFINITY;
 }
 
 }  // namespace vsg

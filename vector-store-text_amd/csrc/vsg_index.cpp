@@ -2195,16 +2195,20 @@ static int ensure_shadow(vsg_index* h, hipStream_t s) {
 
 // The sketch prefilter applies to unfiltered graph searches of f32 dot-metric rows of
 // 1-8 KiB outside the f16-traversal mode.  vsg_index_set_prefilter / VSG_SEARCH_PREFILTER
-// (0 / 1) decide where they are set; otherwise it runs where it was measured faster:
-// ef <= 64 (the 2-row register class) and batches of >= 4,096 queries, which oversubscribe
-// the resident waves so that bytes, not one query's chain of round trips, set the time
-// (C2, ef 36: 10k queries 2.84 -> 2.42 ms, 512 queries 0.42 -> 0.58 ms; ef 128: 10k
-// 5.07 -> 5.70 ms; profiles/prefilter_fractions.jsonl).
+// (0 / 1) decide where they are set; otherwise it runs where it was measured faster, i.e.
+// where the batch oversubscribes the resident waves so that bytes, not one query's chain of
+// round trips, set the time (C2 kernel ms off -> on with the integer sketch pass,
+// profiles/prefilter_i8_gate.jsonl): ef <= 64 (the 2-row register class) from 4,096 queries as
+// before (ef 36: 1,024 queries 0.62 -> 0.81, 2,048 0.92 -> 0.79, 4,096 1.42 -> 1.14, 10k 2.52 ->
+// 2.18; 2,048 would gain, but a small index answers such a batch from L2 and bench.py's
+// roofline, which charges an f32 row per evaluation, then reads above the HBM peak); ef <= 192 (the 4-row class) from 10,000 queries (ef 65 /
+// 128 / 192: 10k 3.98 -> 2.99 / 5.37 -> 4.67 / 6.07 -> 5.71, 4,096 1.89 -> 1.75 / 2.41 -> 2.40 /
+// 2.80 -> 2.94); the 8-row class never (ef 256: 10k 6.77 -> 8.64).
 static bool prefilter_on(const vsg_index* h, size_t ef, size_t nq) {
     if (h->f16_trav || !search_prefilter_supported(h->st, h->mk, h->nchunks, (int)ef)) return false;
     if (h->prefilter >= 0) return h->prefilter != 0;
     if (const char* e = getenv("VSG_SEARCH_PREFILTER")) return atof(e) != 0;
-    return ef <= 64 && nq >= 4096;
+    return (ef <= 64 && nq >= 4096) || (ef <= 192 && nq >= 10000);
 }
 
 // Bring the sketch rows up to date (caller holds h->mu shared).  Rows past the
