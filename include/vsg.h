@@ -71,6 +71,13 @@ extern "C" {
  * adds (usearch's free-slot reuse, vsg_index_add).  Exact-only indexes are
  * always append-only. */
 #define VSG_FLAG_NO_SLOT_REUSE 4u
+/* flags: HNSW search walks the per-row int8 sketch of the (f32) rows -- dimensions + 8
+ * bytes per row, a quarter of the f32 row -- and re-ranks its beam of ef candidates with
+ * exact f32 distances (rerank.hip).  Returned distances are the f32 metric values; the
+ * candidate set can differ from an f32 walk.  No usearch equivalent (opt-in; f32 storage
+ * only, dimensions <= 2048, not together with VSG_FLAG_F16_TRAVERSAL or
+ * VSG_FLAG_EXACT_ONLY; vsg_index_set_i8_traversal). */
+#define VSG_FLAG_I8_TRAVERSAL 8u
 
 typedef struct vsg_index vsg_index_t;
 
@@ -125,6 +132,8 @@ typedef struct {
     uint64_t search_sketch_rows;       /* sketch prefilter (vsg_index_set_prefilter): int8 sketch rows read ... */
     uint64_t search_exact_rows;        /* ... and f32 rows read at level 0 by the prefiltered searches
                                           (search_distances keeps counting every candidate) */
+    uint64_t search_i8_queries;        /* queries answered by the int8 walk (VSG_FLAG_I8_TRAVERSAL); its
+                                          sketch rows also count in search_sketch_rows */
 } vsg_stats_t;
 
 /* replaces usearch::Index::new(&options) — src/index/usearch.rs:98 */
@@ -215,6 +224,23 @@ int vsg_index_exact_search(vsg_index_t* index, const float* queries, size_t nq, 
  * existing index; the f16 copy is built by the next search (and freed when
  * switched off).  VSG_EINVAL unless the storage is f32.  Not in usearch. */
 int vsg_index_set_f16_traversal(vsg_index_t* index, int enable);
+
+/* Switch the int8 traversal + f32 re-rank mode (VSG_FLAG_I8_TRAVERSAL) on an existing
+ * index; the sketch is built by the next search (it is the sketch prefilter's copy:
+ * vsg_index_set_prefilter(index, 0) does not drop it while this mode is on, and switching
+ * this mode off drops it only if the prefilter was switched off).  Not in usearch.
+ * VSG_EINVAL unless the storage is f32, and for an exact-only index or with f16 traversal
+ * on (the two modes exclude each other, in both setters and in vsg_index_new);
+ * VSG_EUNSUPPORTED for dimensions > 2048.
+ * A search runs the int8 walk when the index has no removed entries among its published
+ * slots, upper_ef <= 1 and the register search is in use; any other search of the index
+ * runs the f32 walk as before.  max(ef, k) > 1024 is VSG_EUNSUPPORTED while the mode is on.
+ * A row without a usable sketch (all-zero, non-finite, not converted yet) is scored from its
+ * f32 row; a query without a usable quantisation (all-zero, non-finite, max |q_i| outside
+ * [2^-40, 2^40]) gets the f32 walk's result.  If the sketch cannot be allocated the search
+ * runs the f32 walk and succeeds.  vsg_stats_t.search_i8_queries counts the queries the
+ * int8 walk answered. */
+int vsg_index_set_i8_traversal(vsg_index_t* index, int enable);
 
 /* Sketch prefilter of the graph search (not in usearch; results are unchanged, bit for
  * bit): a per-row int8 sketch (dimensions + 8 bytes per row, built by the next search,

@@ -29,6 +29,7 @@ pub const VSG_NO_KEY: u64 = u64::MAX;
 pub const VSG_FLAG_EXACT_ONLY: u32 = 1;
 pub const VSG_FLAG_F16_TRAVERSAL: u32 = 2;
 pub const VSG_FLAG_NO_SLOT_REUSE: u32 = 4;
+pub const VSG_FLAG_I8_TRAVERSAL: u32 = 8;
 
 #[repr(C)]
 pub struct vsg_index_t {
@@ -85,6 +86,7 @@ pub struct vsg_stats_t {
     pub host_d2h_ns: u64,
     pub search_sketch_rows: u64,
     pub search_exact_rows: u64,
+    pub search_i8_queries: u64,
 }
 
 /// The native actor's options (src/index/usearch.rs:60-66, 101-118 constants made knobs).
@@ -196,6 +198,7 @@ extern "C" {
                                  nq: usize, k_in: usize, k_out: usize, out_keys_device: *mut u64,
                                  out_distances_device: *mut f32, stream: *mut c_void) -> c_int;
     pub fn vsg_index_set_f16_traversal(index: *mut vsg_index_t, enable: c_int) -> c_int;
+    pub fn vsg_index_set_i8_traversal(index: *mut vsg_index_t, enable: c_int) -> c_int;
     pub fn vsg_index_set_upper_ef(index: *mut vsg_index_t, upper_ef: usize) -> c_int;
     pub fn vsg_index_set_prefilter(index: *mut vsg_index_t, on: c_int) -> c_int;
     pub fn vsg_index_stats(index: *const vsg_index_t, out: *mut vsg_stats_t) -> c_int;

@@ -58,7 +58,10 @@ __device__ __forceinline__ void search_reg_one(const SearchParams& p, int qi, ui
     float* od = p.out_dist + (size_t)qi * p.k;
     if (p.entry != VSG_EMPTY) {
         QReg<G, VM, T> q;
-        q.load(p.queries + (size_t)qi * g.row_bytes, g.nchunks);
+        // int8 traversal: the row policy and the query's int8 image (LDS after the visited
+        // table and the staging) instead of a register image
+        if constexpr (RowPolicy<T>::own) q.setup(p, qi, smem + wave_lds_bytes(p.hash_size, 0, 0));
+        else q.load(p.queries + (size_t)qi * g.row_bytes, g.nchunks);
         uint32_t cur = p.entry;
         float dcur = dist_one<G, VM, U, T, MET>(g, q, cur, w);
         ++ndist;
@@ -102,6 +105,14 @@ __device__ __forceinline__ void search_reg_one(const SearchParams& p, int qi, ui
             if (lane == 0 && p.stats) {
                 atomicAdd(&p.stats[18], (unsigned long long)pre_s.nsketch);
                 atomicAdd(&p.stats[19], (unsigned long long)pre_s.nexact);
+            }
+        }
+        if constexpr (RowPolicy<T>::own) {
+            // every evaluation read a sketch row; a query without a usable quantisation ran
+            // the f32 walk and does not count as answered by the int8 walk
+            if (lane == 0 && p.stats && q.usable()) {
+                atomicAdd(&p.stats[18], (unsigned long long)ndist);
+                atomicAdd(&p.stats[32], 1ull);
             }
         }
         // tombstones: skipped in the output, still traversed
@@ -174,12 +185,15 @@ __device__ __forceinline__ void search_reg_one(const SearchParams& p, int qi, ui
 // search cost the C4 shard kernel 15 VGPRs (87 -> 102: 5 -> 4 waves per SIMD, 2.97 ->
 // 3.23 ms at ef 192) although it never ran there.  launch_search_reg sizes the grid by
 // the same constant.
-template <int G, int VM> constexpr bool persist_shape() { return G * VM * 16 >= 1024; }
+// The int8 walk's shapes count their f32 rows: sketch rows of >= 256 B.
+template <int G, int VM, typename T = float> constexpr bool persist_shape() {
+    return G * VM * 16 >= (RowPolicy<T>::own ? 256 : 1024);
+}
 
 template <int G, int VM, int U, typename T, int MET, int R, bool PF = false>
 __global__ __launch_bounds__(64) VSG_SEARCH_ATTR void hnsw_search_reg_kernel(SearchParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    if constexpr (persist_shape<G, VM>()) {
+    if constexpr (persist_shape<G, VM, T>()) {
         if (p.qnext) {
             // persistent grid: resident waves take query indices from a counter until
             // the batch is done
@@ -216,6 +230,8 @@ static inline int reg_rows(int ef) { return ef <= 64 ? 2 : ef <= 192 ? 4 : ef <=
 bool search_prefilter_supported(Storage st, MetricKind mk, int nchunks, int ef) {
     return st == ST_F32 && mk == MK_DOT && nchunks * 16 >= 1024 && nchunks <= 512 && ef >= 1 && ef <= 448;
 }
+
+bool search_i8_supported(size_t sk_stride) { return sk_stride >= 16 && sk_stride / 16 <= (size_t)I8_MAX_CHUNKS; }
 
 size_t search_reg_lds_bytes(int hash) { return wave_lds_bytes(hash, 0, 0); }
 
@@ -267,7 +283,7 @@ hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, h
             constexpr int G = decltype(sh)::G, VM = decltype(sh)::VM, U = decltype(sh)::U;
             using T = typename decltype(tt)::T;
             constexpr int MET = decltype(mt)::MET;
-            auto run = [&](auto kern, size_t lds, bool pf = false) {
+            auto run = [&](auto kern, size_t lds, bool pf = false, bool persist = persist_shape<G, VM>()) {
                 if (lds > 65536)
                     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 constexpr int CH = 1 << 22;  // 64 work-items each: the AQL grid size is 32-bit
@@ -278,8 +294,10 @@ hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, h
                     c.out_keys = p.out_keys + (size_t)off * p.k;
                     c.out_dist = p.out_dist + (size_t)off * p.k;
                     c.out_counts = p.out_counts ? p.out_counts + off : nullptr;
+                    c.i8_gf = G;  // the f32 row shape (int8 traversal: rows scored in f32)
+                    c.i8_vmf = VM;
                     unsigned grid = (unsigned)c.nq;
-                    if (persist_shape<G, VM>() && p.qnext) {  // persistent: one round of resident waves, counter reset per launch
+                    if (persist && p.qnext) {  // persistent: one round of resident waves, counter reset per launch
                         // 3/4 of the resident waves: the kernel is throughput-bound below full
                         // occupancy, and fewer waves end the batch sooner.  C2 fractions 0.35 /
                         // 0.5 / 0.75 / 1.0 with the U=4 row shape (2 waves/SIMD resident): 3.01 /
@@ -301,6 +319,25 @@ hipError_t launch_search_reg(Storage st, MetricKind mk, const SearchParams& p, h
                     err = hipGetLastError();
                 }
             };
+            // int8 traversal: the walk runs on the sketch rows, in the shape of their chunk
+            // count; (G, VM) is the f32 search's shape, whose sums the rows and queries
+            // without a usable sketch are scored with
+            if constexpr (std::is_same<T, float>::value) {
+                if (p.i8) {
+                    if (!p.sk || !search_i8_supported(p.sk_stride)) {
+                        err = hipErrorInvalidValue;
+                        return;
+                    }
+                    dispatch_shape_i8((int)(p.sk_stride / 16), [&](auto ish) {
+                        constexpr int GI = decltype(ish)::G, VMI = decltype(ish)::VM, UI = decltype(ish)::U;
+                        // every resident wave, as the prefilter instances: 3/4 of them cost the C2
+                        // batch 9 % (1.284 -> 1.397 ms, profiles/i8_traversal_shapes.jsonl)
+                        run(hnsw_search_reg_kernel<GI, VMI, UI, SketchI8, MET, R>,
+                            lds_plain + QReg<GI, VMI, SketchI8>::LDS_BYTES, true, persist_shape<GI, VMI, SketchI8>());
+                    });
+                    return;
+                }
+            }
             // the sketch prefilter: f32 dot-metric rows of >= 1 KiB, 2 / 4 / 8 register rows
             if constexpr (prefilter_shape<G, VM, T, MET, R>()) {
                 if (p.sk) {

@@ -211,4 +211,28 @@ static inline VSG_HD float sketch_upper(const SketchQuery& q, SketchMeta m, int 
     return p >= VSG_SKETCH_PMIN ? ub : INFINITY;
 }
 
+// ---- the estimate itself: the walk distance of the int8 traversal ----
+
+// A row's sketch can be evaluated: both meta words finite and the scale positive.  Not so
+// for an all-zero or non-finite row (scale 0, err +inf) and for a row not converted yet
+// (meta words all ones: NaN) -- such a row is scored from its f32 row.
+static inline VSG_HD bool sketch_usable(SketchMeta m) {
+    return m.scale > 0.f && m.scale <= 3.4028234e38f && m.err <= 3.4028234e38f;
+}
+
+// q . x~ in the kernel's f32 arithmetic from the integer sums H and L of sketch_upper,
+// without its error terms: fl(s_q scale) * fma(256, fl(H), fl(L)).  On integer data in
+// [-127, 127] with an element of magnitude 127 on both sides (scale 1, s_q 2^-8, l = 0) and
+// 127^2 d < 2^24 (d <= 1040; stated for d <= 520) every step is exact: the estimate is q . x.
+static inline VSG_HD float sketch_estimate(const SketchQuery& q, SketchMeta m, int H, int L) {
+    const float p = q.sq * m.scale;
+    return p * fmaf(256.f, (float)H, (float)L);
+}
+
+// The metric distance of an estimate: 1 - est (ip, cos), |x|^2 + |q|^2 - 2 est (l2sq; xn =
+// the stored |x|^2, qn = |q|^2 summed once per query).  Exact whenever its terms are integers
+// below 2^24.
+static inline VSG_HD float sketch_dist_dot(float est) { return 1.f - est; }
+static inline VSG_HD float sketch_dist_l2(float est, float xn, float qn) { return fmaf(-2.f, est, xn + qn); }
+
 }  // namespace vsg

@@ -263,9 +263,9 @@ struct RowsProf {
 template <int G, int VM> constexpr bool kSkipLoads() { return G * VM * 16 <= 512; }
 
 template <int G, int VM, int U, typename T, int MET>
-__device__ __forceinline__ void rows_dist(const uint8_t* __restrict__ vecs, size_t row_bytes,
-                                          int nchunks, const uint32_t* ids, int count,
-                                          const QReg<G, VM, T>& q, float* out, RowsProf* rp = nullptr) {
+__device__ __forceinline__ void rows_dist_plain(const uint8_t* __restrict__ vecs, size_t row_bytes,
+                                                int nchunks, const uint32_t* ids, int count,
+                                                const QReg<G, VM, T>& q, float* out, RowsProf* rp = nullptr) {
     constexpr int R = 64 / G;
     constexpr int E = ChunkT<T>::E;
     const int lane = lane_id();
@@ -317,6 +317,22 @@ __device__ __forceinline__ void rows_dist(const uint8_t* __restrict__ vecs, size
         if (rp) rp->valu += VSG_CYC() - tp;
 #endif
     }
+}
+
+// Row-access policy of a storage tag T: `own` = QReg<G, VM, T> is a specialisation that
+// brings its own rows (q.rows<U, MET>(ids, count, out)) instead of the 16-B chunks of
+// `vecs` -- the int8 sketch walk, sketch_device.hpp.  Everything built on rows_dist
+// (dist_one, greedy_level, beam_reg) then runs on that policy unchanged.
+template <typename T> struct RowPolicy {
+    static constexpr bool own = false;
+};
+
+template <int G, int VM, int U, typename T, int MET>
+__device__ __forceinline__ void rows_dist(const uint8_t* __restrict__ vecs, size_t row_bytes,
+                                          int nchunks, const uint32_t* ids, int count,
+                                          const QReg<G, VM, T>& q, float* out, RowsProf* rp = nullptr) {
+    if constexpr (RowPolicy<T>::own) q.template rows<U, MET>(ids, count, out);
+    else rows_dist_plain<G, VM, U, T, MET>(vecs, row_bytes, nchunks, ids, count, q, out, rp);
 }
 
 // rows_dist for two register images at once: each row is loaded once and

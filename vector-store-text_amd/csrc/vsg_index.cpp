@@ -461,6 +461,10 @@ struct vsg_index {
     // converted yet has meta words of all ones (NaN: never rejected).
     // prefilter: -1 = the VSG_SEARCH_PREFILTER default.
     int prefilter = -1;
+    // int8 traversal (vsg_index_set_i8_traversal, VSG_FLAG_I8_TRAVERSAL): eligible searches
+    // walk the sketch rows and re-rank their beam in f32 (sketch_device.hpp SketchI8).  It
+    // shares the sketch copy with the prefilter: either of the two keeps it alive.
+    bool i8_trav = false;
     RowCopy sketch;
     uint8_t* d_sketch = nullptr;
     float* d_sketch_meta = nullptr;  // (scale, err) per row
@@ -1499,6 +1503,17 @@ int vsg_sample_level(uint64_t seed, uint64_t slot, uint32_t connectivity) {
     return sample_level(seed, slot, connectivity);
 }
 
+// May int8 traversal be switched on for this storage, these other flags and this dimension?
+static int i8_traversal_check(Storage st, uint32_t other_flags, int dim) {
+    if (st != ST_F32) return fail(VSG_EINVAL, "int8 traversal needs f32 storage");
+    if (other_flags & VSG_FLAG_EXACT_ONLY) return fail(VSG_EINVAL, "int8 traversal on an exact-only index (no graph)");
+    if (other_flags & VSG_FLAG_F16_TRAVERSAL)
+        return fail(VSG_EINVAL, "int8 traversal and f16 traversal are mutually exclusive");
+    if (!search_i8_supported(sketch_stride(dim)))
+        return fail(VSG_EUNSUPPORTED, "int8 traversal supports dimensions <= 2048 (got " + std::to_string(dim) + ")");
+    return VSG_OK;
+}
+
 int vsg_index_new(const vsg_index_options_t* o, vsg_index_t** out) {
     VSG_RANGE();
     if (!o || !out) return fail(VSG_EINVAL, "null argument");
@@ -1529,6 +1544,14 @@ int vsg_index_new(const vsg_index_options_t* o, vsg_index_t** out) {
     if (h->f16_trav && h->st != ST_F32) {
         delete h;
         return fail(VSG_EINVAL, "VSG_FLAG_F16_TRAVERSAL needs f32 storage");
+    }
+    h->i8_trav = (o->flags & VSG_FLAG_I8_TRAVERSAL) != 0;
+    if (h->i8_trav) {
+        const int rc = i8_traversal_check(h->st, o->flags & ~VSG_FLAG_I8_TRAVERSAL, h->dim);
+        if (rc) {
+            delete h;
+            return rc;
+        }
     }
     h->row_bytes16 = (size_t)(h->dim + 7) / 8 * 16;
     const size_t per_chunk = 16 / h->elem;
@@ -2391,6 +2414,7 @@ struct GraphPlan {
     size_t ef;     // max(ef, k)
     int upper_ef;  // VSG_SEARCH_UPPER_EF / vsg_index_set_upper_ef
     bool rerank;   // f16 traversal: the beam of the f16 search is re-ranked in f32
+    bool i8;       // int8 traversal: the beam of the sketch walk is re-ranked in f32
     bool filt;     // removed entries among the published slots
     bool rerun;    // ... and room for the re-run lists of overflowing queries
 };
@@ -2412,6 +2436,41 @@ static hipError_t run_graph_rerank(vsg_index* h, const SearchCall& c, SearchPara
     p.out_dist = c.region<float>(c.at.cand_dist);
     p.out_counts = cc;
     if (err == hipSuccess) err = launch_search(ST_F16, h->mk, p, c.s);
+    if (err != hipSuccess) return err;
+    RerankParams rp{};
+    rp.vecs = h->d_vecs;
+    rp.row_bytes = h->row_bytes;
+    rp.nchunks = h->nchunks;
+    rp.queries = c.region<const uint8_t>(c.at.queries);
+    rp.cand = ck;
+    rp.cand_counts = cc;
+    rp.nq = (int)c.nq;
+    rp.kc = p.ef;
+    rp.k = (int)c.k;
+    rp.keys = h->d_keys;
+    rp.out_keys = c.ok;
+    rp.out_dist = c.od;
+    rp.out_counts = c.oc;
+    return launch_rerank(h->mk, rp, c.s);
+}
+
+// The int8-traversal leg: the sketch rows are walked with the prepared f32 queries (the
+// kernel quantises each into LDS), the whole beam (slots, not keys) goes to the f32 re-rank.
+static hipError_t run_graph_i8(vsg_index* h, const SearchCall& c, SearchParams p) {
+    uint64_t* ck = c.region<uint64_t>(c.at.cand_keys);
+    uint32_t* cc = c.region<uint32_t>(c.at.cand_counts);
+    p.i8 = 1;
+    p.sk = h->d_sketch;
+    p.sk_meta = h->d_sketch_meta;
+    p.sk_stride = sketch_stride(h->dim);
+    p.sk_dim = h->dim;
+    p.sqnorm = h->d_sqnorm;
+    p.k = p.ef;  // the whole beam goes to the re-rank
+    p.keys = nullptr;
+    p.out_keys = ck;
+    p.out_dist = c.region<float>(c.at.cand_dist);
+    p.out_counts = cc;
+    const hipError_t err = launch_search(ST_F32, h->mk, p, c.s);
     if (err != hipSuccess) return err;
     RerankParams rp{};
     rp.vecs = h->d_vecs;
@@ -2480,6 +2539,7 @@ static int run_graph(vsg_index* h, const SearchCall& c, const GraphPlan& gp, siz
         // indexes without removed entries
         p.upper_ef = 0;
     }
+    if (gp.i8) return search_launch_rc(run_graph_i8(h, c, p));
     // int8 sketch prefilter (same results, fewer f32 rows read): the register kernel,
     // no removed entries
     if (!gp.rerank && !gp.filt && p.reg && slots > 0 && prefilter_on(h, gp.ef, c.nq)) {
@@ -2512,6 +2572,8 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
                                           std::to_string(MAX_EF) + " is not supported (the beam lives in LDS)");
     if (!exact && h->f16_trav && ef_eff > MAX_REG_EF)
         return fail(VSG_EUNSUPPORTED, "f16 traversal + re-rank supports max(ef, k) <= " + std::to_string(MAX_REG_EF));
+    if (!exact && h->i8_trav && ef_eff > MAX_REG_EF)
+        return fail(VSG_EUNSUPPORTED, "int8 traversal + re-rank supports max(ef, k) <= " + std::to_string(MAX_REG_EF));
     const int upper_ef = (int)env_double("VSG_SEARCH_UPPER_EF", h->upper_ef);
     if (!exact && upper_ef > 1 && ef_eff > MAX_REG_EF)
         return fail(VSG_EUNSUPPORTED, "multi-entry descent (upper_ef) supports max(ef, k) <= " + std::to_string(MAX_REG_EF));
@@ -2525,7 +2587,7 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
         plan = plan_exact_mfma(nq, slots, k);
     else if (exact)
         plan = plan_exact_valu(nq, slots, k, (size_t)env_double("VSG_EXACT_MIN_WAVES", 8192));
-    GraphPlan gp{ef_eff, upper_ef, false, false, false};
+    GraphPlan gp{ef_eff, upper_ef, false, false, false, false};
     SearchLayout::Sizes sz;
     sz.queries = nq * h->row_bytes;
     if (use_mfma) sz.qnorms = nq * 4;
@@ -2545,6 +2607,17 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
     gp.rerun = gp.filt && env_double("VSG_SEARCH_FILT_RERUN", 1) != 0;  // 0: degrade instead (probes)
     if (gp.filt) sz.overflow = nq;
     if (gp.rerun) sz.rerun = filt_rerun_bytes(slots);
+    // int8 traversal: no removed entries, the greedy descent, the register search, and the
+    // sketch copy at hand -- every other search of such an index is the f32 walk it was
+    gp.i8 = !exact && h->i8_trav && slots > 0 && !gp.filt && upper_ef <= 1 && env_double("VSG_SEARCH_REG", 1) != 0;
+    if (gp.i8 && !ensure_sketch(h, s)) {
+        h->sketch_failures++;
+        gp.i8 = false;
+    }
+    if (gp.i8) {  // the f16 mode's candidate regions, without its f16 queries
+        sz.cand_keys = nq * ef_eff * 8;
+        sz.cand_dist = sz.cand_counts = nq * ef_eff * 4;
+    }
     SearchCall c{q_dev, nq, k, ok, od, oc, s, nullptr, SearchLayout(sz)};
     Workspace* ws = nullptr;
     int rc = ws_acquire(h, c.at.total, s, &ws);
@@ -2861,7 +2934,27 @@ int vsg_index_set_prefilter(vsg_index_t* h, int on) {
     DeviceGuard dg(h->device);
     std::lock_guard<std::mutex> g(h->sketch.mu);
     h->prefilter = on != 0;
-    if (!on && h->d_sketch) row_copy_drop(h, h->sketch, h->stream, h->d_sketch, h->d_sketch_meta);
+    // the int8 traversal walks the same copy: it stays while that mode is on
+    if (!on && !h->i8_trav && h->d_sketch) row_copy_drop(h, h->sketch, h->stream, h->d_sketch, h->d_sketch_meta);
+    return VSG_OK;
+}
+
+int vsg_index_set_i8_traversal(vsg_index_t* h, int enable) {
+    VSG_RANGE();
+    if (!h) return fail(VSG_EINVAL, "null index");
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (enable) {
+        const int rc = i8_traversal_check(h->st, h->opt.flags & ~VSG_FLAG_I8_TRAVERSAL, h->dim);
+        if (rc) return rc;
+    }
+    DeviceGuard dg(h->device);
+    std::lock_guard<std::mutex> g(h->sketch.mu);
+    h->i8_trav = enable != 0;
+    h->opt.flags = enable ? (h->opt.flags | VSG_FLAG_I8_TRAVERSAL) : (h->opt.flags & ~VSG_FLAG_I8_TRAVERSAL);
+    // mu held exclusively: no host search is in flight.  The copy goes only if the prefilter
+    // was switched off explicitly (left to its default it may want the copy again).
+    if (!enable && h->prefilter == 0 && h->d_sketch)
+        row_copy_drop(h, h->sketch, h->stream, h->d_sketch, h->d_sketch_meta);
     return VSG_OK;
 }
 
@@ -2871,6 +2964,7 @@ int vsg_index_set_f16_traversal(vsg_index_t* h, int enable) {
     std::unique_lock<std::shared_mutex> lk(h->mu);
     if (enable && h->st != ST_F32) return fail(VSG_EINVAL, "f16 traversal needs f32 storage");
     if (enable && (h->opt.flags & VSG_FLAG_EXACT_ONLY)) return fail(VSG_EUNSUPPORTED, "exact-only index");
+    if (enable && h->i8_trav) return fail(VSG_EINVAL, "f16 traversal and int8 traversal are mutually exclusive");
     DeviceGuard dg(h->device);
     std::lock_guard<std::mutex> g(h->shadow.mu);
     h->f16_trav = enable != 0;
@@ -2965,6 +3059,7 @@ int vsg_index_stats(const vsg_index_t* h, vsg_stats_t* out) {
     out->host_d2h_ns = h->hs_d2h_ns.load();
     out->search_sketch_rows = s[18];
     out->search_exact_rows = s[19];
+    out->search_i8_queries = s[32];
     return VSG_OK;
 }
 

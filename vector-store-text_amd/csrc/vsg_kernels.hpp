@@ -65,6 +65,14 @@ struct SearchParams {
     const void* sk_meta;
     size_t sk_stride;
     int sk_dim;
+    // int8 traversal (VSG_FLAG_I8_TRAVERSAL; register kernel, sketch_device.hpp SketchI8):
+    // i8 = 1 walks the sketch rows above (sk set) with the sketch estimate as the distance;
+    // g / queries stay the f32 rows and prepared f32 queries, read only for rows and queries
+    // without a usable sketch.  sqnorm: |x|^2 per slot (l2sq).  keys = nullptr, k = ef: the
+    // beam goes to the re-rank.  stats [18] counts the sketch rows, [32] the queries walked.
+    int i8;
+    const float* sqnorm;
+    int i8_gf, i8_vmf;  // the f32 search's row shape (set by launch_search_reg)
 };
 
 struct InsertParams {
@@ -177,8 +185,9 @@ struct RerankParams {
 };
 
 // kernel counter block (d_stats): [0..2] search, [3..9] build, [10..15] wave
-// clocks (tools), [16] filtered-search overflow, [18] / [19] sketch / f32 rows of the prefiltered search
-constexpr int VSG_NSTATS = 32;
+// clocks (tools), [16] filtered-search overflow, [18] / [19] sketch / f32 rows of the prefiltered search,
+// [20..31] the make prof search breakdown, [32] queries answered by the int8 walk
+constexpr int VSG_NSTATS = 40;
 
 // key layout of the reverse-link pairs
 constexpr int PAIR_U_BITS = 29;
@@ -238,6 +247,8 @@ hipError_t launch_sketch_rows(const uint8_t* vecs, size_t row_bytes, size_t r0, 
                               void* meta, hipStream_t s);
 // the sketch prefilter has an instance for this search (f32 dot-metric rows of 1 to 8 KiB, ef <= 448)
 bool search_prefilter_supported(Storage st, MetricKind mk, int nchunks, int ef);
+// the int8 traversal has an instance for sketch rows of this stride (dimensions <= 2048)
+bool search_i8_supported(size_t sk_stride);
 // rows [r0, r1) of row-major f32 `vecs` (row_floats % 32 == 0) -> the K-tiled layout
 // of MfmaExactParams::ktile
 hipError_t launch_ktile_rows(const float* vecs, int row_floats, size_t r0, size_t r1, float* ktile,

@@ -82,6 +82,7 @@ class Stats(C.Structure):
         ("host_d2h_ns", C.c_uint64),
         ("search_sketch_rows", C.c_uint64),
         ("search_exact_rows", C.c_uint64),
+        ("search_i8_queries", C.c_uint64),
     ]
 
 
@@ -180,6 +181,7 @@ def lib() -> C.CDLL:
         "vsg_index_stats": (C.c_int, [P, C.POINTER(Stats)]),
         "vsg_index_reset_stats": (C.c_int, [P]),
         "vsg_index_set_f16_traversal": (C.c_int, [P, C.c_int]),
+        "vsg_index_set_i8_traversal": (C.c_int, [P, C.c_int]),
         "vsg_index_set_upper_ef": (C.c_int, [P, sz]),
         "vsg_index_set_prefilter": (C.c_int, [P, C.c_int]),
         "vsg_index_graph_info": (C.c_int, [P, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),

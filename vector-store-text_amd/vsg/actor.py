@@ -30,7 +30,7 @@ class Actor:
                  device: int = 0, seed: int = 0, reserve_increment: int = 0, reserve_threshold: int = 0,
                  max_batch: int = 0, max_wait_us: int = 0, compact_percent: int = 0, compact_min_dead: int = 0,
                  f16_traversal: bool = False, concurrent_reads: int = 0, devices=None,
-                 slot_reuse: bool = True):
+                 slot_reuse: bool = True, i8_traversal: bool = False):
         """devices: a list of device ordinals => one shard per entry (vsg_actor_new_sharded,
         include/vsg.h "Sharded index"); None => one index on `device`.
         concurrent_reads: 0 (or False) = submission order; n (or True = 1) = n read workers
@@ -38,9 +38,10 @@ class Actor:
         slot_reuse: False => VSG_FLAG_NO_SLOT_REUSE (append-only adds; compaction reclaims)."""
         self.dimensions = int(dimensions)
         # f16_traversal: opt-in VSG_FLAG_F16_TRAVERSAL (f16 walk + exact f32 re-rank, DESIGN.md §3.5)
+        # i8_traversal: opt-in VSG_FLAG_I8_TRAVERSAL (int8 sketch walk + exact f32 re-rank, DESIGN.md §3.5a)
         opt = ActorOptions(Options(self.dimensions, METRICS[metric], SCALARS[quantization], connectivity,
                                    expansion_add, expansion_search, device,
-                                   (2 if f16_traversal else 0) | (0 if slot_reuse else 4), seed),
+                                   (2 if f16_traversal else 0) | (0 if slot_reuse else 4) | (8 if i8_traversal else 0), seed),
                            reserve_increment, reserve_threshold, max_batch, max_wait_us, compact_percent,
                            int(concurrent_reads), compact_min_dead)
         h = C.c_void_p()

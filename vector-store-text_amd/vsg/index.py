@@ -51,13 +51,14 @@ class Index:
     def __init__(self, dimensions: int, metric: str = "l2sq", quantization: str = "f32",
                  connectivity: int = 0, expansion_add: int = 0, expansion_search: int = 0,
                  device: int = 0, seed: int = 0, exact_only: bool = False,
-                 f16_traversal: bool = False, slot_reuse: bool = True):
+                 f16_traversal: bool = False, slot_reuse: bool = True, i8_traversal: bool = False):
         self.dimensions = int(dimensions)
         self.metric = metric
         self.quantization = quantization
         opt = Options(self.dimensions, METRICS[metric], SCALARS[quantization], connectivity,
                       expansion_add, expansion_search, device,
-                      (1 if exact_only else 0) | (2 if f16_traversal else 0) | (0 if slot_reuse else 4), seed)
+                      (1 if exact_only else 0) | (2 if f16_traversal else 0) | (0 if slot_reuse else 4) |
+                      (8 if i8_traversal else 0), seed)
         h = C.c_void_p()
         check(lib().vsg_index_new(C.byref(opt), C.byref(h)))
         self._h = h
@@ -197,6 +198,12 @@ class Index:
         """Opt-in: HNSW search walks an f16 copy of the rows and re-ranks its ef-beam
         with exact f32 distances (csrc/rerank.hip; no usearch equivalent)."""
         check(lib().vsg_index_set_f16_traversal(self._h, 1 if enable else 0))
+
+    def set_i8_traversal(self, on: bool) -> None:
+        """Opt-in: HNSW search walks the int8 sketch of the f32 rows and re-ranks its
+        ef-beam with exact f32 distances (csrc/sketch_device.hpp SketchI8, csrc/rerank.hip;
+        no usearch equivalent).  Excludes f16 traversal."""
+        check(lib().vsg_index_set_i8_traversal(self._h, 1 if on else 0))
 
     def set_upper_ef(self, upper_ef: int) -> None:
         """Opt-in multi-entry descent: a level-1 beam of this width seeds level 0

@@ -22,7 +22,7 @@ class ShardedIndex:
     def __init__(self, dimensions: int, metric: str = "l2sq", quantization: str = "f32",
                  connectivity: int = 0, expansion_add: int = 0, expansion_search: int = 0,
                  devices=None, n_shards: int = 0, answer_device: int = -1, seed: int = 0,
-                 exact_only: bool = False):
+                 exact_only: bool = False, i8_traversal: bool = False):
         if devices is not None:
             devices = [int(d) for d in devices]
             n_shards = n_shards or len(devices)
@@ -34,7 +34,8 @@ class ShardedIndex:
         self.metric, self.quantization = metric, quantization
         self._devs = (C.c_int32 * n_shards)(*devices) if devices is not None else None
         opt = ShardedOptions(Options(self.dimensions, METRICS[metric], SCALARS[quantization], connectivity,
-                                     expansion_add, expansion_search, 0, 1 if exact_only else 0, seed),
+                                     expansion_add, expansion_search, 0,
+                                     (1 if exact_only else 0) | (8 if i8_traversal else 0), seed),
                              n_shards, answer_device,
                              C.cast(self._devs, C.POINTER(C.c_int32)) if self._devs is not None else None)
         h = C.c_void_p()
