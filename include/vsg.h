@@ -134,6 +134,8 @@ typedef struct {
                                           (search_distances keeps counting every candidate) */
     uint64_t search_i8_queries;        /* queries answered by the int8 walk (VSG_FLAG_I8_TRAVERSAL); its
                                           sketch rows also count in search_sketch_rows */
+    uint64_t exact_mfma_queries;       /* exact-search queries answered by a matrix-core kernel (f32 or
+                                          f16 storage); the others took the VALU kernel */
 } vsg_stats_t;
 
 /* replaces usearch::Index::new(&options) — src/index/usearch.rs:98 */
@@ -216,7 +218,12 @@ size_t vsg_index_free_slots(const vsg_index_t* index, uint32_t* out, size_t cap)
 int vsg_index_search(vsg_index_t* index, const float* queries, size_t nq, size_t k, size_t ef,
                      uint64_t* out_keys, float* out_distances, size_t* out_counts);
 /* Exact brute force over all live vectors (absent in the reference);
- * same signature; ties broken by insertion slot. */
+ * same signature; ties broken by insertion slot.  Batches of >= 32 queries with
+ * k <= 16 over rows of whole 32-element groups run on the matrix cores, f32 storage on
+ * the f32 MFMA and f16 storage on the f16 MFMA (f16 rows x queries rounded to f16,
+ * f32 accumulation); every other search runs the VALU kernel.  Both return the top k
+ * by (distance, slot), equal up to f32 summation order; VSG_EXACT_MFMA=0 selects the
+ * VALU kernel, vsg_stats_t.exact_mfma_queries counts the matrix-core queries. */
 int vsg_index_exact_search(vsg_index_t* index, const float* queries, size_t nq, size_t k,
                            uint64_t* out_keys, float* out_distances, size_t* out_counts);
 

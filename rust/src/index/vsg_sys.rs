@@ -87,6 +87,7 @@ pub struct vsg_stats_t {
     pub search_sketch_rows: u64,
     pub search_exact_rows: u64,
     pub search_i8_queries: u64,
+    pub exact_mfma_queries: u64,
 }
 
 /// The native actor's options (src/index/usearch.rs:60-66, 101-118 constants made knobs).

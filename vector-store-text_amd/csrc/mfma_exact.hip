@@ -21,12 +21,11 @@
 // are merged by merge_parts_kernel.  Ties: (distance, slot) as everywhere.
 #include <hip/hip_runtime.h>
 
+#include "mfma_tile.hpp"
 #include "vsg_device.hpp"
 #include "vsg_kernels.hpp"
 
 namespace vsg {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int KT = 32;   // dims per stage = one 128-B LDS row
 constexpr int LDK = 32;  // LDS row stride (floats), unpadded: glds writes lane-linear 1-KiB pieces
@@ -39,30 +38,6 @@ constexpr int LDK = 32;  // LDS row stride (floats), unpadded: glds writes lane-
 template <int WQ, int WR> struct MfmaTile {
     static constexpr int BQ = 64 * WQ, BR = 64 * WR, NW = WQ * WR, STAGE = (BR + BQ) * LDK;
 };
-
-// 16-B slot of logical chunk c (0..7) in LDS row R: XOR swizzle so the sixteen
-// lanes of a ds_read_b128 group (rows R..R+15, same chunk) hit distinct slots of
-// the 64-bank row (conflict-free); applied to the glds SOURCE and to the read.
-__device__ __forceinline__ int swz(int R, int c) { return c ^ ((R >> 1) & 7); }
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-template <int KMAX>
-__device__ __forceinline__ void topk_insert(float (&ld)[KMAX], uint32_t (&li)[KMAX], float d, uint32_t id) {
-    // ascending list, strict < : an equal distance from a later (larger) slot goes after
-#pragma unroll
-    for (int t = KMAX - 1; t >= 1; --t) {
-        const bool shift = d < ld[t - 1];
-        const bool here = !shift && d < ld[t];
-        ld[t] = shift ? ld[t - 1] : (here ? d : ld[t]);
-        li[t] = shift ? li[t - 1] : (here ? id : li[t]);
-    }
-    if (d < ld[0]) {
-        ld[0] = d;
-        li[0] = id;
-    }
-}
 
 template <int KMAX, int MET, int WQ, int WR>
 __global__ __launch_bounds__(64 * WQ * WR, 2) void mfma_exact_kernel(MfmaExactParams p) {

@@ -468,6 +468,7 @@ struct vsg_index {
     RowCopy sketch;
     uint8_t* d_sketch = nullptr;
     float* d_sketch_meta = nullptr;  // (scale, err) per row
+    std::atomic<uint64_t> exact_mfma_queries{0};  // queries answered by a matrix-core exact kernel
     std::atomic<uint64_t> sketch_failures{0};  // searches that ran unfiltered because the copy failed
     // K-tiled copy of the f32 rows for the MFMA brute force of exact-only indexes
     // (MfmaExactParams::ktile): kept up to date by every add (ensure_ktile before
@@ -2357,7 +2358,36 @@ static hipError_t merge_parts_two_stage(float* pd, uint32_t* pi, const ExactPlan
     return launch_merge_parts(mp, s);
 }
 
+// f16 storage: the stored f16 rows against the f16 prepared queries (mfma_exact_f16.hip);
+// same plan, partial lists and merge
+static int run_exact_mfma_f16(vsg_index* h, const SearchCall& c, const ExactPlan& plan, size_t slots) {
+    float* pd = c.region<float>(c.at.part_d);
+    uint32_t* pi = c.region<uint32_t>(c.at.part_i);
+    MfmaExactF16Params mp{};
+    mp.vecs = h->d_vecs;
+    mp.sqnorm = h->d_sqnorm;
+    mp.queries = c.region<const uint8_t>(c.at.queries);
+    mp.qsqnorm = c.region<const float>(c.at.qnorms);
+    mp.row_bytes = (int)h->row_bytes;
+    mp.nq = (int)c.nq;
+    mp.nslots = slots;
+    mp.flags = h->d_flags;
+    mp.qtiles = plan.qtiles;
+    mp.splits = (int)plan.splits;
+    mp.tiles_per_split = (int)plan.tiles_per_split;
+    mp.kmax = plan.kmax;
+    mp.bq = plan.bq;
+    mp.br = plan.br;
+    mp.part_d = pd;
+    mp.part_i = pi;
+    hipError_t err = launch_mfma_exact_f16(h->mk, mp, c.s);
+    if (err == hipSuccess)
+        err = merge_parts_two_stage(pd, pi, plan, c.nq, c.k, plan.kmax, h->d_keys, c.ok, c.od, c.oc, c.s);
+    return search_launch_rc(err);
+}
+
 static int run_exact_mfma(vsg_index* h, const SearchCall& c, const ExactPlan& plan, size_t slots) {
+    if (h->st == ST_F16) return run_exact_mfma_f16(h, c, plan, slots);
     float* pd = c.region<float>(c.at.part_d);
     uint32_t* pi = c.region<uint32_t>(c.at.part_i);
     MfmaExactParams mp{};
@@ -2577,10 +2607,12 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
     const int upper_ef = (int)env_double("VSG_SEARCH_UPPER_EF", h->upper_ef);
     if (!exact && upper_ef > 1 && ef_eff > MAX_REG_EF)
         return fail(VSG_EUNSUPPORTED, "multi-entry descent (upper_ef) supports max(ef, k) <= " + std::to_string(MAX_REG_EF));
-    // exact search on the f32 matrix cores when the batch amortises a 128-query tile
+    // exact search on the matrix cores (f32 rows: mfma_exact.hip, f16 rows: mfma_exact_f16.hip)
+    // when the batch amortises a query tile and the rows are whole 32-element groups
     const size_t mfma_min = (size_t)env_double("VSG_EXACT_MFMA_MIN", 32);
-    const bool use_mfma = exact && h->st == ST_F32 && k <= 16 && (h->row_bytes / 4) % 32 == 0 &&
-                          nq >= mfma_min && h->pub_slots > 0 && env_double("VSG_EXACT_MFMA", 1) != 0;
+    const size_t elem_bytes = h->st == ST_F16 ? 2 : 4;
+    const bool use_mfma = exact && k <= 16 && (h->row_bytes / elem_bytes) % 32 == 0 && nq >= mfma_min &&
+                          h->pub_slots > 0 && env_double("VSG_EXACT_MFMA", 1) != 0;
     const size_t slots = h->pub_slots;  // rows of the last completed add
     ExactPlan plan;
     if (use_mfma)
@@ -2633,6 +2665,7 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
     c.base = ws->base;
     rc = search_launch_rc(launch_prepare(h->st, q_dev, nq, h->dim, h->normalize, c.base + c.at.queries, h->row_bytes, s,
                                          use_mfma ? c.region<float>(c.at.qnorms) : nullptr));
+    if (rc == VSG_OK && use_mfma) h->exact_mfma_queries += nq;
     if (rc == VSG_OK)
         rc = use_mfma ? run_exact_mfma(h, c, plan, slots) : exact ? run_exact_valu(h, c, plan, slots) : run_graph(h, c, gp, slots);
     ws_release(h, ws, s);
@@ -3060,6 +3093,7 @@ int vsg_index_stats(const vsg_index_t* h, vsg_stats_t* out) {
     out->search_sketch_rows = s[18];
     out->search_exact_rows = s[19];
     out->search_i8_queries = s[32];
+    out->exact_mfma_queries = h->exact_mfma_queries.load();
     return VSG_OK;
 }
 
@@ -3091,6 +3125,7 @@ int vsg_index_reset_stats(vsg_index_t* h) {
     h->t_reverse_ns = 0;
     h->slots_reused = 0;
     h->ktile_failures = 0;
+    h->exact_mfma_queries = 0;
     h->hs_calls = 0;
     h->hs_ns = 0;
     h->hs_h2d_ns = 0;

@@ -153,6 +153,26 @@ struct MfmaExactParams {
     const float* ktile;
 };
 
+// Brute force on the f16 matrix cores (f16 storage, mfma_exact_f16.hip): the same
+// blocks, tiles and partial lists as MfmaExactParams over byte-addressed f16 rows of
+// row_bytes (a multiple of 64: whole 32-half groups); no K-tiled copy.
+struct MfmaExactF16Params {
+    const uint8_t* vecs;     // N x row_bytes (stored f16 rows)
+    const float* sqnorm;     // N: |stored row|^2 (L2 only)
+    const uint8_t* queries;  // nq x row_bytes (prepared: rounded to f16)
+    const float* qsqnorm;    // nq: |prepared query|^2 (L2 only)
+    int row_bytes;
+    int nq;
+    size_t nslots;
+    const uint8_t* flags;
+    int qtiles, splits;
+    int tiles_per_split;
+    int kmax;
+    int bq, br;
+    float* part_d;
+    uint32_t* part_i;
+};
+
 struct MergeParams {
     const float* part_d;
     const uint32_t* part_i;
@@ -257,6 +277,9 @@ constexpr int KTILE_ROWS = 256;
 // returns hipErrorNotSupported when the MFMA path does not apply (k > 32)
 hipError_t launch_mfma_exact(MetricKind mk, const MfmaExactParams& p, hipStream_t s);
 constexpr int MFMA_BQ = 128, MFMA_BR = 128;
+// the f16-storage sibling: hipErrorNotSupported for another tile or kmax,
+// hipErrorInvalidValue for rows that are not whole 32-half groups
+hipError_t launch_mfma_exact_f16(MetricKind mk, const MfmaExactF16Params& p, hipStream_t s);
 hipError_t launch_merge_topk64(const uint64_t* keys, const float* dist, int parts, int nq, int kin, int kout,
                                uint64_t* out_keys, float* out_dist, hipStream_t s);
 // f32 rows (stride dim) -> storage rows (row_bytes), normalised when `normalize`

@@ -83,6 +83,7 @@ class Stats(C.Structure):
         ("search_sketch_rows", C.c_uint64),
         ("search_exact_rows", C.c_uint64),
         ("search_i8_queries", C.c_uint64),
+        ("exact_mfma_queries", C.c_uint64),
     ]
 
 
