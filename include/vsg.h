@@ -221,9 +221,13 @@ int vsg_index_search(vsg_index_t* index, const float* queries, size_t nq, size_t
  * same signature; ties broken by insertion slot.  Batches of >= 32 queries with
  * k <= 16 over rows of whole 32-element groups run on the matrix cores, f32 storage on
  * the f32 MFMA and f16 storage on the f16 MFMA (f16 rows x queries rounded to f16,
- * f32 accumulation); every other search runs the VALU kernel.  Both return the top k
- * by (distance, slot), equal up to f32 summation order; VSG_EXACT_MFMA=0 selects the
- * VALU kernel, vsg_stats_t.exact_mfma_queries counts the matrix-core queries. */
+ * f32 accumulation).  The same batches with 17 <= k <= 128 over at least 4,096 rows
+ * (VSG_EXACT_WIDE_MIN_ROWS) run a third matrix-core kernel for either storage, which
+ * selects through a per-query threshold and a candidate pool instead of a register
+ * list.  Every other search (k > 128, fewer queries or rows, ragged dimensions) runs
+ * the VALU kernel.  All return the top k by (distance, slot), equal up to f32 summation
+ * order; VSG_EXACT_MFMA=0 selects the VALU kernel, vsg_stats_t.exact_mfma_queries counts
+ * the matrix-core queries. */
 int vsg_index_exact_search(vsg_index_t* index, const float* queries, size_t nq, size_t k,
                            uint64_t* out_keys, float* out_distances, size_t* out_counts);
 

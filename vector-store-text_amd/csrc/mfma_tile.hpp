@@ -1,6 +1,6 @@
-// mfma_tile.hpp — what the matrix-core exact kernels (mfma_exact.hip, mfma_exact_f16.hip)
-// share: the swizzle of a 128-B LDS row, the LDS-DMA pointer types and the per-lane
-// sorted top-KMAX list.
+// mfma_tile.hpp — what the matrix-core exact kernels (mfma_exact.hip, mfma_exact_f16.hip,
+// mfma_exact_wide.hip) share: the swizzle of a 128-B LDS row, the LDS-DMA pointer types
+// and the per-lane sorted top-KMAX list (the first two only).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // search_plan.hpp — the arithmetic of one device search, host only (no HIP include):
-// the partial-list shape of the two exact kernels, the visited-table size of the graph
+// the partial-list shape of the exact kernels, the visited-table size of the graph
 // search and the carve-up of the search workspace.  Pure functions of their arguments,
 // structs by value: vsg_index.cpp's search_device_locked calls them on every search,
 // tests/cpp/test_search_plan.cpp sweeps them on the CPU (a mistake here drops rows
@@ -64,6 +64,46 @@ static inline ExactPlan plan_exact_mfma(size_t nq, size_t slots, size_t k) {
     return p;
 }
 
+// Wide-k matrix-core brute force (mfma_exact_wide.hip): 17 <= k <= PLAN_WIDE_MAX_K, nq >= 1,
+// slots >= 1.  The 128 x 128 tile only (a batch of 32..64 queries computes on padding
+// queries).  One sorted k-list per (query, split): nparts = splits, kmax = k.  Behind the
+// lists the kernel needs a candidate pool of PLAN_WIDE_POOL 8-byte entries per (padded
+// query, split): `pool` entries, <= 512 MiB + 4 KiB per padded query (at most 1,023
+// blocks' pools once the 64-list rounding is in, or one split).  split_cap: the probe
+// VSG_EXACT_WIDE_SPLITS (0: no cap).
+constexpr int PLAN_WIDE_MAX_K = 128, PLAN_WIDE_POOL = 512;
+struct ExactWidePlan : ExactPlan {
+    size_t qpad = 0;  // queries of whole tiles
+    size_t pool = 0;  // pool entries (8 B each): qpad x splits x PLAN_WIDE_POOL
+};
+static inline ExactWidePlan plan_exact_mfma_wide(size_t nq, size_t slots, size_t k, size_t split_cap) {
+    ExactWidePlan p;
+    p.bq = PLAN_MFMA_BQ;
+    p.br = PLAN_MFMA_BR;
+    p.qtiles = (int)((nq + p.bq - 1) / p.bq);
+    p.qpad = (size_t)p.qtiles * p.bq;
+    const size_t ntiles = (slots + p.br - 1) / p.br;
+    // one round of resident blocks (2 per CU), not the two of plan_exact_mfma: a split's
+    // threshold rejects more the more rows it has seen, and its k-list is merged once
+    const size_t target = 512;
+    size_t splits = std::min<size_t>(ntiles, std::max<size_t>(1, (target + p.qtiles - 1) / p.qtiles));
+    if (split_cap) splits = std::min(splits, split_cap);
+    const size_t tps = (ntiles + splits - 1) / splits;
+    splits = (ntiles + tps - 1) / tps;
+    p.kmax = (int)k;
+    if (splits > PLAN_MERGE_LISTS) {  // padding splits hold no rows and write empty lists
+        splits = (splits + 63) / 64 * 64;
+        p.ngroups = (int)(splits / 64);
+    }
+    p.splits = splits;
+    p.tiles_per_split = tps;
+    p.nparts = (int)splits;
+    p.np_lists = nq * splits * k;
+    p.np = p.np_lists + (p.ngroups ? nq * (size_t)p.ngroups * k : 0);
+    p.pool = p.qpad * splits * PLAN_WIDE_POOL;
+    return p;
+}
+
 // VALU brute force (any storage, k <= MAX_EXACT_K): min_waves is VSG_EXACT_MIN_WAVES
 static inline ExactPlan plan_exact_valu(size_t nq, size_t slots, size_t k, size_t min_waves) {
     ExactPlan p;
@@ -119,9 +159,10 @@ struct SearchLayout {
         size_t cand_counts = 0;  //   candidate counts
         size_t overflow = 0;     // filtered search: per-query overflow flags,
         size_t rerun = 0;        //   the re-run lists in device memory
+        size_t pool = 0;         // wide-k exact: the candidate pools
     };
     size_t queries = 0, qnorms = 0, part_d = 0, part_i = 0, q16 = 0, cand_keys = 0, cand_dist = 0, cand_counts = 0,
-           overflow = 0, rerun = 0, counter = 0, total = 0;
+           overflow = 0, rerun = 0, pool = 0, counter = 0, total = 0;
     SearchLayout() = default;
     explicit SearchLayout(const Sizes& b) {
         size_t at = 0;
@@ -140,6 +181,7 @@ struct SearchLayout {
         cand_counts = take(b.cand_counts);
         overflow = take(b.overflow);
         rerun = take(b.rerun);
+        pool = take(b.pool);
         counter = take(256);  // persistent-grid counter (one word)
         total = at;
     }

@@ -2302,6 +2302,11 @@ static int ensure_ktile(vsg_index* h, size_t slots, hipStream_t s) {
 #undef ROW_TRY
 
 static_assert(PLAN_MFMA_BQ == MFMA_BQ && PLAN_MFMA_BR == MFMA_BR, "search_plan.hpp plans the tile the MFMA kernel runs");
+static_assert(PLAN_WIDE_MAX_K == MFMA_WIDE_MAX_K && PLAN_WIDE_POOL == MFMA_WIDE_POOL,
+              "search_plan.hpp plans the pools the wide-k kernel fills");
+// fewest published rows at which a 17 <= k <= 128 exact search takes the wide-k kernel
+// (VSG_EXACT_WIDE_MIN_ROWS overrides): plan_exact_valu's row block
+constexpr size_t EXACT_WIDE_MIN_ROWS = 4096;
 
 // One device search between ws_acquire and ws_release: the caller's arguments and the
 // carved-up workspace.
@@ -2413,6 +2418,33 @@ static int run_exact_mfma(vsg_index* h, const SearchCall& c, const ExactPlan& pl
     mp.part_d = pd;
     mp.part_i = pi;
     hipError_t err = launch_mfma_exact(h->mk, mp, c.s);
+    if (err == hipSuccess)
+        err = merge_parts_two_stage(pd, pi, plan, c.nq, c.k, plan.kmax, h->d_keys, c.ok, c.od, c.oc, c.s);
+    return search_launch_rc(err);
+}
+
+// 17 <= k <= 128, either storage (mfma_exact_wide.hip): one sorted k-list per (query, split),
+// selected through the candidate pools; the same merge
+static int run_exact_mfma_wide(vsg_index* h, const SearchCall& c, const ExactWidePlan& plan, size_t slots) {
+    float* pd = c.region<float>(c.at.part_d);
+    uint32_t* pi = c.region<uint32_t>(c.at.part_i);
+    MfmaExactWideParams mp{};
+    mp.vecs = h->d_vecs;
+    mp.sqnorm = h->d_sqnorm;
+    mp.queries = c.region<const uint8_t>(c.at.queries);
+    mp.qsqnorm = c.region<const float>(c.at.qnorms);
+    mp.row_bytes = (int)h->row_bytes;
+    mp.nq = (int)c.nq;
+    mp.nslots = slots;
+    mp.flags = h->d_flags;
+    mp.qtiles = plan.qtiles;
+    mp.splits = (int)plan.splits;
+    mp.tiles_per_split = (int)plan.tiles_per_split;
+    mp.k = (int)c.k;
+    mp.pool = c.region<uint64_t>(c.at.pool);
+    mp.part_d = pd;
+    mp.part_i = pi;
+    hipError_t err = launch_mfma_exact_wide(h->st, h->mk, mp, c.s);
     if (err == hipSuccess)
         err = merge_parts_two_stage(pd, pi, plan, c.nq, c.k, plan.kmax, h->d_keys, c.ok, c.od, c.oc, c.s);
     return search_launch_rc(err);
@@ -2611,19 +2643,28 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
     // when the batch amortises a query tile and the rows are whole 32-element groups
     const size_t mfma_min = (size_t)env_double("VSG_EXACT_MFMA_MIN", 32);
     const size_t elem_bytes = h->st == ST_F16 ? 2 : 4;
-    const bool use_mfma = exact && k <= 16 && (h->row_bytes / elem_bytes) % 32 == 0 && nq >= mfma_min &&
-                          h->pub_slots > 0 && env_double("VSG_EXACT_MFMA", 1) != 0;
+    const bool mfma_shape = exact && (h->row_bytes / elem_bytes) % 32 == 0 && nq >= mfma_min && h->pub_slots > 0 &&
+                            env_double("VSG_EXACT_MFMA", 1) != 0;
+    // 17 <= k <= 128: the wide-k kernel (mfma_exact_wide.hip), from EXACT_WIDE_MIN_ROWS rows
+    // on -- the VALU kernel's own row block: below it a VALU launch is one block per query
+    // with nothing to merge, and a threshold filter rejects little until rows >> k
+    const bool use_wide = mfma_shape && k > 16 && k <= (size_t)MFMA_WIDE_MAX_K &&
+                          h->pub_slots >= (size_t)env_double("VSG_EXACT_WIDE_MIN_ROWS", EXACT_WIDE_MIN_ROWS);
+    const bool use_mfma = (mfma_shape && k <= 16) || use_wide;
     const size_t slots = h->pub_slots;  // rows of the last completed add
-    ExactPlan plan;
-    if (use_mfma)
-        plan = plan_exact_mfma(nq, slots, k);
+    ExactWidePlan plan;
+    if (use_wide)
+        plan = plan_exact_mfma_wide(nq, slots, k, (size_t)env_double("VSG_EXACT_WIDE_SPLITS", 0));  // probe: 0 = no cap
+    else if (use_mfma)
+        static_cast<ExactPlan&>(plan) = plan_exact_mfma(nq, slots, k);
     else if (exact)
-        plan = plan_exact_valu(nq, slots, k, (size_t)env_double("VSG_EXACT_MIN_WAVES", 8192));
+        static_cast<ExactPlan&>(plan) = plan_exact_valu(nq, slots, k, (size_t)env_double("VSG_EXACT_MIN_WAVES", 8192));
     GraphPlan gp{ef_eff, upper_ef, false, false, false, false};
     SearchLayout::Sizes sz;
     sz.queries = nq * h->row_bytes;
     if (use_mfma) sz.qnorms = nq * 4;
     sz.part = plan.np * 4;
+    sz.pool = plan.pool * 8;
     gp.rerank = !exact && h->f16_trav && slots > 0;
     if (gp.rerank) {
         const int rc0 = ensure_shadow(h, s);
@@ -2667,7 +2708,10 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
                                          use_mfma ? c.region<float>(c.at.qnorms) : nullptr));
     if (rc == VSG_OK && use_mfma) h->exact_mfma_queries += nq;
     if (rc == VSG_OK)
-        rc = use_mfma ? run_exact_mfma(h, c, plan, slots) : exact ? run_exact_valu(h, c, plan, slots) : run_graph(h, c, gp, slots);
+        rc = use_wide   ? run_exact_mfma_wide(h, c, plan, slots)
+             : use_mfma ? run_exact_mfma(h, c, plan, slots)
+             : exact    ? run_exact_valu(h, c, plan, slots)
+                        : run_graph(h, c, gp, slots);
     ws_release(h, ws, s);
     return rc;
 }

@@ -173,6 +173,27 @@ struct MfmaExactF16Params {
     uint32_t* part_i;
 };
 
+// Brute force on the matrix cores with a long result list (mfma_exact_wide.hip, 17 <= k <=
+// MFMA_WIDE_MAX_K): the 128 x 128 tile of the two kernels above over byte-addressed rows
+// of either storage; the selection is a threshold per query in LDS and a candidate pool
+// per (query, split) in device memory.  One sorted k-list per (query, split).
+struct MfmaExactWideParams {
+    const uint8_t* vecs;     // N x row_bytes (prepared f32 rows or stored f16 rows)
+    const float* sqnorm;     // N (L2 only)
+    const uint8_t* queries;  // nq x row_bytes (prepared)
+    const float* qsqnorm;    // nq (L2 only)
+    int row_bytes;           // f32: a multiple of 128, f16: of 64
+    int nq;
+    size_t nslots;
+    const uint8_t* flags;
+    int qtiles, splits;
+    int tiles_per_split;     // 128-row tiles per split
+    int k;
+    uint64_t* pool;          // qtiles * 128 x splits x MFMA_WIDE_POOL packed (distance, slot) keys
+    float* part_d;           // nq x splits x k
+    uint32_t* part_i;
+};
+
 struct MergeParams {
     const float* part_d;
     const uint32_t* part_i;
@@ -280,6 +301,11 @@ constexpr int MFMA_BQ = 128, MFMA_BR = 128;
 // the f16-storage sibling: hipErrorNotSupported for another tile or kmax,
 // hipErrorInvalidValue for rows that are not whole 32-half groups
 hipError_t launch_mfma_exact_f16(MetricKind mk, const MfmaExactF16Params& p, hipStream_t s);
+// the wide-k sibling of both: hipErrorNotSupported outside 17 <= k <= MFMA_WIDE_MAX_K,
+// hipErrorInvalidValue for rows that are not whole 32-element groups
+hipError_t launch_mfma_exact_wide(Storage st, MetricKind mk, const MfmaExactWideParams& p, hipStream_t s);
+constexpr int MFMA_WIDE_MAX_K = 128;
+constexpr int MFMA_WIDE_POOL = 512;  // candidate-pool entries per (query, split)
 hipError_t launch_merge_topk64(const uint64_t* keys, const float* dist, int parts, int nq, int kin, int kout,
                                uint64_t* out_keys, float* out_dist, hipStream_t s);
 // f32 rows (stride dim) -> storage rows (row_bytes), normalised when `normalize`
