@@ -136,6 +136,8 @@ typedef struct {
                                           sketch rows also count in search_sketch_rows */
     uint64_t exact_mfma_queries;       /* exact-search queries answered by a matrix-core kernel (f32 or
                                           f16 storage); the others took the VALU kernel */
+    uint64_t search_team_queries;      /* queries answered by the multi-wave search kernel
+                                          (vsg_index_set_search_team) */
 } vsg_stats_t;
 
 /* replaces usearch::Index::new(&options) — src/index/usearch.rs:98 */
@@ -273,6 +275,20 @@ int vsg_index_set_prefilter(vsg_index_t* index, int on);
  * removed entries searches with the greedy descent (its overflow re-run walks a
  * sorted list in device memory that has no multi-entry form). */
 int vsg_index_set_upper_ef(vsg_index_t* index, size_t upper_ef);
+
+/* Opt-in multi-wave search for small batches (not in usearch; results are unchanged, bit
+ * for bit): a team of `waves` waves (2 or 4) serves each query -- one wave walks the graph
+ * as the one-wave search does, all of them score the rows of each expansion -- so a batch
+ * of a few hundred queries uses the compute units one wave per query leaves idle.  0 or 1 =
+ * off (default); any other value is VSG_EINVAL; an exact-only index is VSG_EUNSUPPORTED.
+ * A search runs on teams when the register search is in use, max(ef, k) <= 192,
+ * upper_ef <= 1, the index has no removed entries among its published slots, neither the
+ * f16 nor the int8 traversal is active for it, and the batch is small enough for every
+ * team to be resident on the device at once (VSG_SEARCH_TEAM_MAX_QUERIES overrides that
+ * capacity); every other search runs as before.  Until this is called the environment
+ * variable VSG_SEARCH_TEAM (0 / 2 / 4) decides.  Runtime state like upper_ef: not saved
+ * with the index.  vsg_stats_t.search_team_queries counts the queries teams answered. */
+int vsg_index_set_search_team(vsg_index_t* index, uint32_t waves);
 
 /* Device-resident variants: queries (f32 nq x dimensions), outputs and counts
  * (u32, optional) in device memory; enqueued on `stream` (NULL => the HIP

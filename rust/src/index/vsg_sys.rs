@@ -88,6 +88,7 @@ pub struct vsg_stats_t {
     pub search_exact_rows: u64,
     pub search_i8_queries: u64,
     pub exact_mfma_queries: u64,
+    pub search_team_queries: u64,
 }
 
 /// The native actor's options (src/index/usearch.rs:60-66, 101-118 constants made knobs).
@@ -202,6 +203,7 @@ extern "C" {
     pub fn vsg_index_set_i8_traversal(index: *mut vsg_index_t, enable: c_int) -> c_int;
     pub fn vsg_index_set_upper_ef(index: *mut vsg_index_t, upper_ef: usize) -> c_int;
     pub fn vsg_index_set_prefilter(index: *mut vsg_index_t, on: c_int) -> c_int;
+    pub fn vsg_index_set_search_team(index: *mut vsg_index_t, waves: u32) -> c_int;
     pub fn vsg_index_stats(index: *const vsg_index_t, out: *mut vsg_stats_t) -> c_int;
     pub fn vsg_index_reset_stats(index: *mut vsg_index_t) -> c_int;
     pub fn vsg_index_graph_info(index: *const vsg_index_t, slots: *mut usize, upper_rows: *mut usize,

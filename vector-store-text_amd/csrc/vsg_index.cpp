@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/vsg.h"
+#include "hnsw_search_team.hpp"
 #include "keymap.hpp"
 #include "roctx_range.hpp"
 #include "search_plan.hpp"
@@ -468,6 +469,10 @@ struct vsg_index {
     RowCopy sketch;
     uint8_t* d_sketch = nullptr;
     float* d_sketch_meta = nullptr;  // (scale, err) per row
+    // multi-wave search teams (vsg_index_set_search_team; hnsw_search_team.hip): 0 = off, 2 / 4 =
+    // waves per query, -1 = the VSG_SEARCH_TEAM default.  Runtime state, not saved.
+    int search_team = -1;
+    std::atomic<uint64_t> search_team_queries{0};  // queries answered by the team kernel
     std::atomic<uint64_t> exact_mfma_queries{0};  // queries answered by a matrix-core exact kernel
     std::atomic<uint64_t> sketch_failures{0};  // searches that ran unfiltered because the copy failed
     // K-tiled copy of the f32 rows for the MFMA brute force of exact-only indexes
@@ -2471,6 +2476,13 @@ static int run_exact_valu(vsg_index* h, const SearchCall& c, const ExactPlan& pl
     return search_launch_rc(err);
 }
 
+// Waves per query of the multi-wave search (0: the one-wave kernels).  The setter decides
+// once called; until then VSG_SEARCH_TEAM (0 / 2 / 4; anything else is off).
+static int search_team_waves(const vsg_index* h) {
+    const int w = h->search_team >= 0 ? h->search_team : (int)env_double("VSG_SEARCH_TEAM", 0);
+    return w == 2 || w == 4 ? w : 0;
+}
+
 // What a graph search was planned with beyond its layout.
 struct GraphPlan {
     size_t ef;     // max(ef, k)
@@ -2600,6 +2612,21 @@ static int run_graph(vsg_index* h, const SearchCall& c, const GraphPlan& gp, siz
         // as one that did not; multi-entry descent applies to
         // indexes without removed entries
         p.upper_ef = 0;
+    }
+    // Multi-wave teams (opt-in; hnsw_search_team.hip): the plain register search -- greedy
+    // descent, no removed entries, neither traversal mode, ef within the 2- and 4-row classes --
+    // of a batch whose teams are all resident at once (VSG_SEARCH_TEAM_MAX_QUERIES overrides
+    // the capacity: probes, tests).  Same results; every other search runs as it did.
+    if (const int team = search_team_waves(h); team && p.reg && gp.ef <= (size_t)TEAM_MAX_EF && p.upper_ef <= 1 && !gp.filt &&
+                                               !gp.rerank && !gp.i8) {
+        const double cap_env = env_double("VSG_SEARCH_TEAM_MAX_QUERIES", -1);
+        const size_t cap = cap_env >= 0 ? (size_t)cap_env
+                                        : (size_t)search_team_capacity(h->st, h->mk, h->nchunks, p.ef, p.hash_size, team);
+        if (c.nq <= std::min(cap, (size_t)1 << 22)) {
+            const int rc = search_launch_rc(launch_search_team(h->st, h->mk, p, team, c.s));
+            if (rc == VSG_OK) h->search_team_queries += c.nq;
+            return rc;
+        }
     }
     if (gp.i8) return search_launch_rc(run_graph_i8(h, c, p));
     // int8 sketch prefilter (same results, fewer f32 rows read): the register kernel,
@@ -3004,6 +3031,15 @@ int vsg_index_set_upper_ef(vsg_index_t* h, size_t upper_ef) {
     return VSG_OK;
 }
 
+int vsg_index_set_search_team(vsg_index_t* h, uint32_t waves) {
+    if (!h) return fail(VSG_EINVAL, "null index");
+    if (waves != 0 && waves != 1 && waves != 2 && waves != 4) return fail(VSG_EINVAL, "search team: waves must be 0, 1, 2 or 4");
+    if (h->opt.flags & VSG_FLAG_EXACT_ONLY) return fail(VSG_EUNSUPPORTED, "exact-only index");
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    h->search_team = waves >= 2 ? (int)waves : 0;
+    return VSG_OK;
+}
+
 int vsg_index_set_prefilter(vsg_index_t* h, int on) {
     VSG_RANGE();
     if (!h) return fail(VSG_EINVAL, "null index");
@@ -3138,6 +3174,7 @@ int vsg_index_stats(const vsg_index_t* h, vsg_stats_t* out) {
     out->search_exact_rows = s[19];
     out->search_i8_queries = s[32];
     out->exact_mfma_queries = h->exact_mfma_queries.load();
+    out->search_team_queries = h->search_team_queries.load();
     return VSG_OK;
 }
 
@@ -3170,6 +3207,7 @@ int vsg_index_reset_stats(vsg_index_t* h) {
     h->slots_reused = 0;
     h->ktile_failures = 0;
     h->exact_mfma_queries = 0;
+    h->search_team_queries = 0;
     h->hs_calls = 0;
     h->hs_ns = 0;
     h->hs_h2d_ns = 0;

@@ -84,6 +84,7 @@ class Stats(C.Structure):
         ("search_exact_rows", C.c_uint64),
         ("search_i8_queries", C.c_uint64),
         ("exact_mfma_queries", C.c_uint64),
+        ("search_team_queries", C.c_uint64),
     ]
 
 
@@ -184,6 +185,7 @@ def lib() -> C.CDLL:
         "vsg_index_set_f16_traversal": (C.c_int, [P, C.c_int]),
         "vsg_index_set_i8_traversal": (C.c_int, [P, C.c_int]),
         "vsg_index_set_upper_ef": (C.c_int, [P, sz]),
+        "vsg_index_set_search_team": (C.c_int, [P, u32]),
         "vsg_index_set_prefilter": (C.c_int, [P, C.c_int]),
         "vsg_index_graph_info": (C.c_int, [P, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                                            C.POINTER(u32), C.POINTER(C.c_int)]),

@@ -210,6 +210,12 @@ class Index:
         (0/1 = usearch greedy descent, the default)."""
         check(lib().vsg_index_set_upper_ef(self._h, int(upper_ef)))
 
+    def set_search_team(self, waves: int) -> None:
+        """Opt-in multi-wave search for small batches: 2 or 4 waves per query score each
+        expansion's rows together (0/1 = off, the default; same results, bit for bit;
+        csrc/hnsw_search_team.hip)."""
+        check(lib().vsg_index_set_search_team(self._h, int(waves)))
+
     def set_prefilter(self, on: bool) -> None:
         """Sketch prefilter of the graph search (same results; on by default where it
         applies: f32 cos / ip rows of >= 1 KiB; csrc/sketch.hpp)."""
