@@ -55,6 +55,21 @@ extern "C" {
 
 #define VSG_SCALAR_F32 0
 #define VSG_SCALAR_F16 1
+/* bf16 storage (usearch ScalarKind::BF16): 2 bytes per element like f16, with f32's
+ * 8-bit exponent and 7 stored mantissa bits -- no rescaling of unnormalised data, where
+ * f16 overflows above 65,504 and flushes below ~6e-8.  Contract of a bf16 index:
+ *  - rows are rounded from f32 (after normalisation for cos) to the nearest bf16, ties
+ *    to even; NaN stays NaN, +-inf stays +-inf, a finite value beyond the largest bf16
+ *    (~3.39e38) becomes inf; export / get widen exactly, so export -> import is the
+ *    identity;
+ *  - queries arrive as f32 and are rounded the same way before any distance: every
+ *    path (HNSW search, filtered search, search teams, exact search on the VALU and on
+ *    the matrix cores) compares bf16 rows with bf16-rounded queries, accumulating in f32;
+ *  - the f32-only modes stay f32-only, with the errors / silent non-use an f16 index
+ *    gives: the sketch prefilter (vsg_index_set_prefilter), VSG_FLAG_F16_TRAVERSAL,
+ *    VSG_FLAG_I8_TRAVERSAL and the K-tiled copy of exact-only indexes;
+ *  - files store the rows as they are, with this value in the header. */
+#define VSG_SCALAR_BF16 2
 
 #define VSG_NO_KEY UINT64_MAX /* padding key for short result rows */
 
@@ -134,8 +149,8 @@ typedef struct {
                                           (search_distances keeps counting every candidate) */
     uint64_t search_i8_queries;        /* queries answered by the int8 walk (VSG_FLAG_I8_TRAVERSAL); its
                                           sketch rows also count in search_sketch_rows */
-    uint64_t exact_mfma_queries;       /* exact-search queries answered by a matrix-core kernel (f32 or
-                                          f16 storage); the others took the VALU kernel */
+    uint64_t exact_mfma_queries;       /* exact-search queries answered by a matrix-core kernel (f32,
+                                          f16 or bf16 storage); the others took the VALU kernel */
     uint64_t search_team_queries;      /* queries answered by the multi-wave search kernel
                                           (vsg_index_set_search_team) */
 } vsg_stats_t;

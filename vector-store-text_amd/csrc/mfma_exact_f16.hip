@@ -1,7 +1,9 @@
 // mfma_exact_f16.hip — batched brute-force k-NN of an f16 index on the f16 matrix
 // cores (gfx950): D = X . Q^T over the stored f16 rows and the f16 prepared queries
 // with `v_mfma_f32_32x32x16_f16` (f16 x f16 products exact in f32, f32 accumulation),
-// fused with the per-lane register top-KMAX of mfma_exact.hip.
+// fused with the per-lane register top-KMAX of mfma_exact.hip.  A bf16 index runs the
+// same kernel on `v_mfma_f32_32x32x16_bf16` (the element type is a template parameter;
+// "half" below reads "2-byte element").
 //
 //   block = 256 threads (4 waves), tile = 128 rows x 128 queries (2 x 2 waves), or
 //   256 rows x 64 queries (4 x 1) for batches <= 64; wave (wr, wq) owns 64 x 64 =
@@ -35,12 +37,14 @@
 
 namespace vsg {
 
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-
 constexpr int HROW = 128;  // bytes per LDS row = one K stage of a row (64 halves)
 
-template <int KMAX, int MET, int WQ, int WR>
+// T: the stored element, _Float16 or bf16_t (bf16 rows and bf16-rounded queries on
+// `v_mfma_f32_32x32x16_bf16`: bf16 x bf16 products are exact in f32 as well).  Two-byte
+// elements either way, so stages, swizzle, DMA pieces and epilogue are the same code.
+template <typename T, int KMAX, int MET, int WQ, int WR>
 __global__ __launch_bounds__(64 * WQ * WR, 2) void mfma_exact_f16_kernel(MfmaExactF16Params p) {
+    using V8 = typename Mfma16<T>::V;
     constexpr int BQ = 64 * WQ, BR = 64 * WR, NW = WQ * WR, STAGE = (BR + BQ) * HROW;
     __shared__ __attribute__((aligned(16))) uint8_t lds_a[STAGE];
     __shared__ __attribute__((aligned(16))) uint8_t lds_b[STAGE];
@@ -148,22 +152,22 @@ __global__ __launch_bounds__(64 * WQ * WR, 2) void mfma_exact_f16_kernel(MfmaExa
 #pragma unroll
             for (int tq = 0; tq < 4; ++tq) {
                 if (tq < ntq) {
-                    halfx8 xa[2], qb[2];
+                    V8 xa[2], qb[2];
 #pragma unroll
                     for (int a = 0; a < 2; ++a) {
                         const int R = wr * 64 + a * 32 + r;
-                        xa[a] = *reinterpret_cast<const halfx8*>(xs + R * HROW + swz(R, tq * 2 + h) * 16);
+                        xa[a] = *reinterpret_cast<const V8*>(xs + R * HROW + swz(R, tq * 2 + h) * 16);
                     }
 #pragma unroll
                     for (int b = 0; b < 2; ++b) {
                         const int R = wq * 64 + b * 32 + r;
-                        qb[b] = *reinterpret_cast<const halfx8*>(qs + R * HROW + swz(R, tq * 2 + h) * 16);
+                        qb[b] = *reinterpret_cast<const V8*>(qs + R * HROW + swz(R, tq * 2 + h) * 16);
                     }
 #pragma unroll
                     for (int a = 0; a < 2; ++a)
 #pragma unroll
                         for (int b = 0; b < 2; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xa[a], qb[b], acc[a][b], 0, 0, 0);
+                            acc[a][b] = Mfma16<T>::mma(xa[a], qb[b], acc[a][b]);
                 }
             }
         };
@@ -239,20 +243,27 @@ __global__ __launch_bounds__(64 * WQ * WR, 2) void mfma_exact_f16_kernel(MfmaExa
     }
 }
 
-hipError_t launch_mfma_exact_f16(MetricKind mk, const MfmaExactF16Params& p, hipStream_t s) {
-    // (bq, br) = (128, 128) or (64, 256), both 256-thread blocks; rows of whole 32-half groups
+template <typename T>
+static hipError_t launch_mfma_exact_2byte(MetricKind mk, const MfmaExactF16Params& p, hipStream_t s) {
+    // (bq, br) = (128, 128) or (64, 256), both 256-thread blocks; rows of whole 32-element groups
     if (p.kmax != 16 || !((p.bq == 128 && p.br == 128) || (p.bq == 64 && p.br == 256))) return hipErrorNotSupported;
     if (p.row_bytes <= 0 || p.row_bytes % 64 || p.nslots == 0 || p.nq <= 0) return hipErrorInvalidValue;
     const int total = p.qtiles * p.splits;
     const int nb = (total + 7) / 8 * 8;
     if (p.bq == 128) {
-        auto kern = mk == MK_L2 ? mfma_exact_f16_kernel<16, MET_L2, 2, 2> : mfma_exact_f16_kernel<16, MET_DOT, 2, 2>;
+        auto kern = mk == MK_L2 ? mfma_exact_f16_kernel<T, 16, MET_L2, 2, 2> : mfma_exact_f16_kernel<T, 16, MET_DOT, 2, 2>;
         hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, s, p);
     } else {
-        auto kern = mk == MK_L2 ? mfma_exact_f16_kernel<16, MET_L2, 1, 4> : mfma_exact_f16_kernel<16, MET_DOT, 1, 4>;
+        auto kern = mk == MK_L2 ? mfma_exact_f16_kernel<T, 16, MET_L2, 1, 4> : mfma_exact_f16_kernel<T, 16, MET_DOT, 1, 4>;
         hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, s, p);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_mfma_exact_f16(Storage st, MetricKind mk, const MfmaExactF16Params& p, hipStream_t s) {
+    if (st == ST_F16) return launch_mfma_exact_2byte<_Float16>(mk, p, s);
+    if (st == ST_BF16) return launch_mfma_exact_2byte<bf16_t>(mk, p, s);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace vsg

@@ -11,7 +11,8 @@
 // stage's MFMAs.  Both storages are byte-addressed row-major rows (no K-tiled copy):
 //   f32: `v_mfma_f32_32x32x2_f32`, half-wave h takes floats [16 h, 16 h + 16) of the stage;
 //   f16: `v_mfma_f32_32x32x16_f16`, MFMA step t reads chunk 2 t + h; an odd number of
-//        32-half groups leaves half a stage (mfma_exact_f16.hip).
+//        32-half groups leaves half a stage (mfma_exact_f16.hip);
+//   bf16: the f16 code on `v_mfma_f32_32x32x16_bf16`.
 // Stage 0 of the next row tile is issued right after the tile's last MFMAs and lands
 // during the epilogue; flags and |x|^2 are fetched one row per lane at the top of the
 // tile, so the epilogue's only memory traffic are the stores of its survivors.
@@ -33,11 +34,10 @@
 #include "mfma_tile.hpp"
 #include "mfma_wide_select.hpp"
 #include "vsg_device.hpp"
+#include "vsg_dispatch.hpp"
 #include "vsg_kernels.hpp"
 
 namespace vsg {
-
-typedef _Float16 wide_halfx8 __attribute__((ext_vector_type(8)));
 
 constexpr int WROW = 128;             // bytes per LDS row = one K stage of a row
 constexpr int WB = 128;               // rows and queries per tile
@@ -46,8 +46,11 @@ constexpr int WPOOL = MFMA_WIDE_POOL;
 static_assert(WPOOL >= 2 * WB && (WPOOL & (WPOOL - 1)) == 0, "a tile's 128 appends fit behind a compacted pool");
 static_assert(4 * WPOOL * 8 <= WSTAGE, "the four waves' sort scratch fits in one stage buffer");
 
-template <int MET, bool F16>
+// T: the stored element -- float, _Float16 or bf16_t (the f16 stage code on
+// `v_mfma_f32_32x32x16_bf16`; "F16" below means a 2-byte element).
+template <int MET, typename T>
 __global__ __launch_bounds__(256, 2) void mfma_exact_wide_kernel(MfmaExactWideParams p) {
+    constexpr bool F16 = sizeof(T) == 2;
     __shared__ __attribute__((aligned(16))) uint8_t lds_a[WSTAGE];
     __shared__ __attribute__((aligned(16))) uint8_t lds_b[WSTAGE];
     __shared__ float tau[WB];
@@ -183,13 +186,13 @@ __global__ __launch_bounds__(256, 2) void mfma_exact_wide_kernel(MfmaExactWidePa
                         qb[b] = *reinterpret_cast<const uint4*>(qs + R * WROW + swz(R, c) * 16);
                     }
                     if constexpr (F16) {
+                        using V8 = typename Mfma16<T>::V;
 #pragma unroll
                         for (int a = 0; a < 2; ++a)
 #pragma unroll
                             for (int b = 0; b < 2; ++b)
-                                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                                    __builtin_bit_cast(wide_halfx8, xa[a]), __builtin_bit_cast(wide_halfx8, qb[b]),
-                                    acc[a][b], 0, 0, 0);
+                                acc[a][b] = Mfma16<T>::mma(__builtin_bit_cast(V8, xa[a]), __builtin_bit_cast(V8, qb[b]),
+                                                           acc[a][b]);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
@@ -278,13 +281,16 @@ __global__ __launch_bounds__(256, 2) void mfma_exact_wide_kernel(MfmaExactWidePa
 
 hipError_t launch_mfma_exact_wide(Storage st, MetricKind mk, const MfmaExactWideParams& p, hipStream_t s) {
     if (p.k <= 16 || p.k > MFMA_WIDE_MAX_K) return hipErrorNotSupported;
-    if (p.row_bytes <= 0 || p.row_bytes % (st == ST_F16 ? 64 : 128) || p.nslots == 0 || p.nq <= 0 || p.splits <= 0 ||
+    if (p.row_bytes <= 0 || p.row_bytes % (st == ST_F32 ? 128 : 64) || p.nslots == 0 || p.nq <= 0 || p.splits <= 0 ||
         p.tiles_per_split <= 0 || p.qtiles != (p.nq + WB - 1) / WB || !p.pool)
         return hipErrorInvalidValue;
     const int total = p.qtiles * p.splits;
     const int nb = (total + 7) / 8 * 8;
-    auto kern = st == ST_F16 ? (mk == MK_L2 ? mfma_exact_wide_kernel<MET_L2, true> : mfma_exact_wide_kernel<MET_DOT, true>)
-                             : (mk == MK_L2 ? mfma_exact_wide_kernel<MET_L2, false> : mfma_exact_wide_kernel<MET_DOT, false>);
+    auto pick = [&](auto tt) {
+        using T = typename decltype(tt)::T;
+        return mk == MK_L2 ? mfma_exact_wide_kernel<MET_L2, T> : mfma_exact_wide_kernel<MET_DOT, T>;
+    };
+    auto kern = st == ST_F16 ? pick(TypeTag<_Float16>{}) : st == ST_BF16 ? pick(TypeTag<bf16_t>{}) : pick(TypeTag<float>{});
     hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, s, p);
     return hipGetLastError();
 }

@@ -5,9 +5,28 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vsg_device.hpp"
+
 namespace vsg {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+// The K = 16 matrix instruction of a 2-byte storage type: one 16-B chunk is a lane's
+// whole operand V, and both instructions take the same operand layout at the same
+// rate, so a kernel written for one runs the other by swapping this trait alone.
+template <typename T> struct Mfma16;
+template <> struct Mfma16<_Float16> {
+    typedef _Float16 V __attribute__((ext_vector_type(8)));
+    static __device__ __forceinline__ floatx16 mma(V a, V b, floatx16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Mfma16<bf16_t> {
+    typedef __bf16 V __attribute__((ext_vector_type(8)));
+    static __device__ __forceinline__ floatx16 mma(V a, V b, floatx16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+};
 
 // 16-B slot of logical chunk c (0..7) in LDS row R: XOR swizzle so the sixteen
 // lanes of a ds_read_b128 group (rows R..R+15, same chunk) hit distinct slots of

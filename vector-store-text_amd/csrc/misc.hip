@@ -20,6 +20,26 @@ static inline unsigned capped_grid(size_t items, size_t per_block, size_t cap = 
     return (unsigned)(g < cap ? g : cap);
 }
 
+// f32 -> storage element and back.  f16: the hardware convert (round to nearest even).
+// bf16: round to nearest even on the f32 bits -- adding 0x7fff plus the lowest kept bit
+// carries into the kept half exactly when the dropped half is above, or at and odd
+// below, the midpoint; the carry runs on into the exponent, so a finite value beyond the
+// largest bf16 becomes inf and inf stays inf.  A NaN would turn into inf if its payload
+// sat in the dropped half only, so it keeps its upper half with the quiet bit set.
+template <typename T> __device__ __forceinline__ T to_storage(float v) {
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        const uint32_t u = __float_as_uint(v);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return bf16_t{(uint16_t)((u >> 16) | 0x0040u)};
+        return bf16_t{(uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16)};
+    } else {
+        return (T)v;
+    }
+}
+template <typename T> __device__ __forceinline__ float from_storage(T t) {
+    if constexpr (std::is_same<T, bf16_t>::value) return __uint_as_float((uint32_t)t.bits << 16);
+    else return (float)t;
+}
+
 // One wave per row.  Cos rows are stored unit-normalised (x / |x|) so the
 // traversal kernels evaluate cos as 1 - dot.
 template <typename T>
@@ -43,9 +63,9 @@ __global__ __launch_bounds__(256) void prepare_kernel(const float* __restrict__ 
         for (int j = lane; j < padded; j += 64) {
             float v = 0.f;
             if (j < dim) v = (normalize && nrm > 0.f) ? x[j] / nrm : (normalize ? 0.f : x[j]);
-            const T t = (T)v;
+            const T t = to_storage<T>(v);
             y[j] = t;
-            s2 += (float)t * (float)t;
+            s2 += from_storage<T>(t) * from_storage<T>(t);
         }
         if (sqnorm) {  // |stored row|^2 for the MFMA L2 expansion |x|^2 + |q|^2 - 2 x.q
 #pragma unroll
@@ -62,7 +82,7 @@ __global__ void unprepare_kernel(const uint8_t* __restrict__ in, size_t n, int d
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (size_t)gridDim.x * blockDim.x) {
         const size_t r = i / dim;
         const int j = (int)(i % dim);
-        out[i] = (float)reinterpret_cast<const T*>(in + r * row_bytes)[j];
+        out[i] = from_storage<T>(reinterpret_cast<const T*>(in + r * row_bytes)[j]);
     }
 }
 
@@ -73,8 +93,11 @@ hipError_t launch_prepare(Storage st, const float* in, size_t n, int dim, bool n
     if (st == ST_F32)
         hipLaunchKernelGGL(prepare_kernel<float>, grid, dim3(256), 0, s, in, n, dim, normalize ? 1 : 0, out, row_bytes,
                            sqnorm);
-    else
+    else if (st == ST_F16)
         hipLaunchKernelGGL(prepare_kernel<_Float16>, grid, dim3(256), 0, s, in, n, dim, normalize ? 1 : 0, out,
+                           row_bytes, sqnorm);
+    else
+        hipLaunchKernelGGL(prepare_kernel<bf16_t>, grid, dim3(256), 0, s, in, n, dim, normalize ? 1 : 0, out,
                            row_bytes, sqnorm);
     return hipGetLastError();
 }
@@ -86,8 +109,10 @@ hipError_t launch_unprepare(Storage st, const uint8_t* in, size_t n, int dim, si
     const dim3 grid(capped_grid(tot, 256));
     if (st == ST_F32)
         hipLaunchKernelGGL(unprepare_kernel<float>, grid, dim3(256), 0, s, in, n, dim, row_bytes, out);
-    else
+    else if (st == ST_F16)
         hipLaunchKernelGGL(unprepare_kernel<_Float16>, grid, dim3(256), 0, s, in, n, dim, row_bytes, out);
+    else
+        hipLaunchKernelGGL(unprepare_kernel<bf16_t>, grid, dim3(256), 0, s, in, n, dim, row_bytes, out);
     return hipGetLastError();
 }
 

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define VSG_EMPTY 0xFFFFFFFFu
 #define VSG_EXP_BIT 0x80000000u
 // list entry of a removed node (filtered search: traversed, never a result)
@@ -26,8 +28,34 @@ enum { MET_L2 = 0, MET_DOT = 1 };
 template <typename T> struct ChunkT;
 template <> struct ChunkT<float> { static constexpr int E = 4; };
 template <> struct ChunkT<_Float16> { static constexpr int E = 8; };
+// bf16 storage tag: the upper 16 bits of an f32 (1 sign, 8 exponent, 7 mantissa bits).
+// Only ever widened (no arithmetic of its own), so it is a plain 2-byte word.
+struct bf16_t {
+    uint16_t bits;
+};
+template <> struct ChunkT<bf16_t> { static constexpr int E = 8; };
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+
+// 16-B chunk of a 2-byte storage type -> 8 floats, exactly.  f16: the packed converts;
+// bf16: each 32-bit word holds two elements whose f32 images are the word shifted up
+// (even element) and the word with its low half cleared (odd element) -- one VALU
+// op per element, no conversion.
+template <typename T>
+__device__ __forceinline__ void widen8(const uint4 raw, float (&out)[8]) {
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            out[2 * i] = __uint_as_float(w[i] << 16);
+            out[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        }
+    } else {
+        half8_t h = __builtin_bit_cast(half8_t, raw);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[e] = (float)h[e];
+    }
+}
 
 template <typename T>
 __device__ __forceinline__ void load_chunk(const uint8_t* __restrict__ row, int c,
@@ -39,9 +67,7 @@ __device__ __forceinline__ void load_chunk(const uint8_t* __restrict__ row, int 
         out[2] = __uint_as_float(raw.z);
         out[3] = __uint_as_float(raw.w);
     } else {
-        half8_t h = __builtin_bit_cast(half8_t, raw);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) out[e] = (float)h[e];
+        widen8<T>(raw, out);
     }
 }
 
@@ -180,9 +206,7 @@ template <int G, int VM, typename T> struct QReg {
                 x[v][2] = __uint_as_float(raw[v].z);
                 x[v][3] = __uint_as_float(raw[v].w);
             } else {
-                half8_t h = __builtin_bit_cast(half8_t, raw[v]);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[v][e] = (float)h[e];
+                widen8<T>(raw[v], x[v]);
             }
             if (c >= nchunks) {
 #pragma unroll
@@ -192,7 +216,7 @@ template <int G, int VM, typename T> struct QReg {
     }
 };
 
-// 16-B chunk -> E floats (f16 converted exactly to f32)
+// 16-B chunk -> E floats (f16 / bf16 widened exactly to f32)
 template <typename T>
 __device__ __forceinline__ void unpack_chunk(const uint4 raw, float (&out)[ChunkT<T>::E]) {
     if constexpr (sizeof(T) == 4) {
@@ -201,9 +225,7 @@ __device__ __forceinline__ void unpack_chunk(const uint4 raw, float (&out)[Chunk
         out[2] = __uint_as_float(raw.z);
         out[3] = __uint_as_float(raw.w);
     } else {
-        half8_t h = __builtin_bit_cast(half8_t, raw);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) out[e] = (float)h[e];
+        widen8<T>(raw, out);
     }
 }
 

@@ -132,9 +132,12 @@ inline void dispatch_all(Storage st, MetricKind mk, int nc, F&& f) {
         if (st == ST_F32) {
             if (mk == MK_L2) f(sh, TypeTag<float>{}, MetTag<MET_L2>{});
             else f(sh, TypeTag<float>{}, MetTag<MET_DOT>{});
-        } else {
+        } else if (st == ST_F16) {
             if (mk == MK_L2) f(sh, TypeTag<_Float16>{}, MetTag<MET_L2>{});
             else f(sh, TypeTag<_Float16>{}, MetTag<MET_DOT>{});
+        } else {
+            if (mk == MK_L2) f(sh, TypeTag<bf16_t>{}, MetTag<MET_L2>{});
+            else f(sh, TypeTag<bf16_t>{}, MetTag<MET_DOT>{});
         }
     });
 }

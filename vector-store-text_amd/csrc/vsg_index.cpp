@@ -791,17 +791,17 @@ static int ensure_lists(vsg_index* h, size_t lists) {
 // sampled from the call, found by the f32 MFMA exact kernel) and dealt
 // XCD-contiguously (block b runs on XCD b % 8) makes the waves resident on one
 // XCD insert neighbouring vectors, whose beams share rows in its L2 and the
-// MALL.  The MFMA kernel reads f32 rows: f16 rows are widened chunk by chunk.
+// MALL.  The MFMA kernel reads f32 rows: f16 / bf16 rows are widened chunk by chunk.
 constexpr size_t LOC_PIVOTS = 4096, LOC_CHUNK = 262144;
 
 // f32 elements per row as the MFMA kernel sees it (the padded storage row)
-static size_t loc_row_floats(const vsg_index* h) { return h->st == ST_F32 ? h->row_bytes / 4 : h->row_bytes / 2; }
+static size_t loc_row_floats(const vsg_index* h) { return h->row_bytes / storage_elem_bytes(h->st); }
 
 // rows per cell launch: the MFMA kernel's partial lists (nq x parts x 16 x 8 B,
-// ~134 MB at 256k rows) and, for f16 rows, the widened chunk (capped at 128 MB)
+// ~134 MB at 256k rows) and, for f16 / bf16 rows, the widened chunk (capped at 128 MB)
 static size_t loc_chunk(const vsg_index* h, size_t n) {
     size_t c = LOC_CHUNK;
-    if (h->st == ST_F16) c = std::min(c, std::max(LOC_PIVOTS, ((size_t)32 << 20) / loc_row_floats(h)));
+    if (h->st != ST_F32) c = std::min(c, std::max(LOC_PIVOTS, ((size_t)32 << 20) / loc_row_floats(h)));
     return std::min(c, n);
 }
 
@@ -809,7 +809,7 @@ static int ensure_locality(vsg_index* h, size_t n, size_t max_b, size_t part_ent
     const size_t rf = loc_row_floats(h);
     if (!h->d_piv) HIP_TRY(dev_alloc(&h->d_piv, LOC_PIVOTS * (rf * 4 + 4 + 1 + 4 + 8) + 256, h->stream));
     if (!h->d_pivbf) HIP_TRY(dev_alloc(&h->d_pivbf, cells_pivot_bytes((int)LOC_PIVOTS, (int)rf), h->stream));
-    if (h->st == ST_F16 && chunk > h->cf32_cap) {
+    if (h->st != ST_F32 && chunk > h->cf32_cap) {
         dfree(h, h->d_cf32);
         h->cf32_cap = 0;
         HIP_TRY(dev_alloc(&h->d_cf32, chunk * rf, h->stream));
@@ -886,11 +886,11 @@ static hipError_t rows_to_cells(vsg_index* h, const uint8_t* rows, const float* 
                                 float* part_d, uint32_t* part_i, uint32_t* out, hipStream_t st);
 
 // rows [s0 + c0, s0 + c0 + nq) as the MFMA kernel reads them: the storage rows
-// themselves (f32), or widened into the chunk buffer (f16)
+// themselves (f32), or widened into the chunk buffer (f16 / bf16)
 static const uint8_t* loc_rows(vsg_index* h, size_t first, size_t nq, hipStream_t st, hipError_t& e) {
     const uint8_t* src = h->d_vecs + first * h->row_bytes;
     if (h->st == ST_F32) return src;
-    e = launch_unprepare(ST_F16, src, nq, (int)loc_row_floats(h), h->row_bytes, h->d_cf32, st);
+    e = launch_unprepare(h->st, src, nq, (int)loc_row_floats(h), h->row_bytes, h->d_cf32, st);
     return reinterpret_cast<const uint8_t*>(h->d_cf32);
 }
 
@@ -899,7 +899,7 @@ static const uint8_t* loc_rows(vsg_index* h, size_t first, size_t nq, hipStream_
 static int compute_cells(vsg_index* h, uint32_t s0, size_t n, std::vector<uint32_t>& idx, hipStream_t st) {
     // pivot count (probe knob): 1,024 = the C2 build's best of 512 / 1,024 / 2,048
     const size_t P = std::min({LOC_PIVOTS, n, (size_t)env_double("VSG_BUILD_LOCALITY_PIVOTS", 1024)});
-    // the f16 pivot rows are staged in the widened-chunk buffer: chunk >= P
+    // the f16 / bf16 pivot rows are staged in the widened-chunk buffer: chunk >= P
     const size_t chunk = std::max(loc_chunk(h, n), P);
     // bf16 MFMA nearest pivot (cells.hip); VSG_BUILD_CELLS_F32=1: round 2's f32 exact
     // kernel + top-16 partial lists (same cells up to bf16 near-ties, 6-8x the time)
@@ -919,11 +919,11 @@ static int compute_cells(vsg_index* h, uint32_t s0, size_t n, std::vector<uint32
     if (h->st == ST_F32) {
         HIP_TRY(launch_gather_rows(h->d_vecs, h->d_sqnorm, h->d_keys, pv.idx, P, h->row_bytes, pv.rows, pv.sq,
                                    pv.keys, st));
-    } else {  // gather f16 rows into the chunk buffer, widen into the pivot rows
+    } else {  // gather f16 / bf16 rows into the chunk buffer, widen into the pivot rows
         uint8_t* tmp = reinterpret_cast<uint8_t*>(h->d_cf32);
         HIP_TRY(launch_gather_rows(h->d_vecs, h->d_sqnorm, h->d_keys, pv.idx, P, h->row_bytes, tmp, pv.sq, pv.keys,
                                    st));
-        HIP_TRY(launch_unprepare(ST_F16, tmp, P, (int)loc_row_floats(h), h->row_bytes,
+        HIP_TRY(launch_unprepare(h->st, tmp, P, (int)loc_row_floats(h), h->row_bytes,
                                  reinterpret_cast<float*>(pv.rows), st));
     }
     for (size_t c0 = 0; c0 < n; c0 += chunk) {
@@ -1526,14 +1526,14 @@ int vsg_index_new(const vsg_index_options_t* o, vsg_index_t** out) {
     *out = nullptr;
     if (o->dimensions == 0) return fail(VSG_EINVAL, "dimensions == 0");
     if (o->metric > VSG_METRIC_COS) return fail(VSG_EINVAL, "unknown metric");
-    if (o->quantization > VSG_SCALAR_F16) return fail(VSG_EINVAL, "unknown quantization");
+    if (o->quantization > VSG_SCALAR_BF16) return fail(VSG_EINVAL, "unknown quantization");
     const uint32_t M = o->connectivity ? o->connectivity : 16;
     if (M < 2 || M > (uint32_t)MAX_CONNECTIVITY)
         return fail(VSG_EUNSUPPORTED, "connectivity must be in [2, " + std::to_string(MAX_CONNECTIVITY) + "]");
     auto* h = new vsg_index();
     h->opt = *o;
     h->dim = (int)o->dimensions;
-    h->st = o->quantization == VSG_SCALAR_F16 ? ST_F16 : ST_F32;
+    h->st = o->quantization == VSG_SCALAR_F16 ? ST_F16 : o->quantization == VSG_SCALAR_BF16 ? ST_BF16 : ST_F32;
     h->mk = o->metric == VSG_METRIC_L2SQ ? MK_L2 : MK_DOT;
     h->normalize = o->metric == VSG_METRIC_COS;
     h->M = (int)M;
@@ -1545,7 +1545,7 @@ int vsg_index_new(const vsg_index_options_t* o, vsg_index_t** out) {
         return fail(VSG_EUNSUPPORTED, "expansion_add > " + std::to_string(MAX_EF) +
                                           " is not supported (the build beam keeps its efC list in LDS)");
     }
-    h->elem = h->st == ST_F16 ? 2 : 4;
+    h->elem = storage_elem_bytes(h->st);
     h->f16_trav = (o->flags & VSG_FLAG_F16_TRAVERSAL) != 0;
     if (h->f16_trav && h->st != ST_F32) {
         delete h;
@@ -1566,7 +1566,7 @@ int vsg_index_new(const vsg_index_options_t* o, vsg_index_t** out) {
     h->nchunks = (int)(h->row_bytes / 16);
     if (!shape_supported(h->nchunks)) {
         delete h;
-        return fail(VSG_EUNSUPPORTED, "dimensions too large (max 4096 f32 / 8192 f16)");
+        return fail(VSG_EUNSUPPORTED, "dimensions too large (max 4096 f32 / 8192 f16, bf16)");
     }
     h->device = o->device;
     int ndev = 0;
@@ -2368,8 +2368,8 @@ static hipError_t merge_parts_two_stage(float* pd, uint32_t* pi, const ExactPlan
     return launch_merge_parts(mp, s);
 }
 
-// f16 storage: the stored f16 rows against the f16 prepared queries (mfma_exact_f16.hip);
-// same plan, partial lists and merge
+// f16 / bf16 storage: the stored rows against the queries prepared into the same type
+// (mfma_exact_f16.hip); same plan, partial lists and merge
 static int run_exact_mfma_f16(vsg_index* h, const SearchCall& c, const ExactPlan& plan, size_t slots) {
     float* pd = c.region<float>(c.at.part_d);
     uint32_t* pi = c.region<uint32_t>(c.at.part_i);
@@ -2390,14 +2390,14 @@ static int run_exact_mfma_f16(vsg_index* h, const SearchCall& c, const ExactPlan
     mp.br = plan.br;
     mp.part_d = pd;
     mp.part_i = pi;
-    hipError_t err = launch_mfma_exact_f16(h->mk, mp, c.s);
+    hipError_t err = launch_mfma_exact_f16(h->st, h->mk, mp, c.s);
     if (err == hipSuccess)
         err = merge_parts_two_stage(pd, pi, plan, c.nq, c.k, plan.kmax, h->d_keys, c.ok, c.od, c.oc, c.s);
     return search_launch_rc(err);
 }
 
 static int run_exact_mfma(vsg_index* h, const SearchCall& c, const ExactPlan& plan, size_t slots) {
-    if (h->st == ST_F16) return run_exact_mfma_f16(h, c, plan, slots);
+    if (h->st != ST_F32) return run_exact_mfma_f16(h, c, plan, slots);
     float* pd = c.region<float>(c.at.part_d);
     uint32_t* pi = c.region<uint32_t>(c.at.part_i);
     MfmaExactParams mp{};
@@ -2428,7 +2428,7 @@ static int run_exact_mfma(vsg_index* h, const SearchCall& c, const ExactPlan& pl
     return search_launch_rc(err);
 }
 
-// 17 <= k <= 128, either storage (mfma_exact_wide.hip): one sorted k-list per (query, split),
+// 17 <= k <= 128, any storage (mfma_exact_wide.hip): one sorted k-list per (query, split),
 // selected through the candidate pools; the same merge
 static int run_exact_mfma_wide(vsg_index* h, const SearchCall& c, const ExactWidePlan& plan, size_t slots) {
     float* pd = c.region<float>(c.at.part_d);
@@ -2666,10 +2666,10 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
     const int upper_ef = (int)env_double("VSG_SEARCH_UPPER_EF", h->upper_ef);
     if (!exact && upper_ef > 1 && ef_eff > MAX_REG_EF)
         return fail(VSG_EUNSUPPORTED, "multi-entry descent (upper_ef) supports max(ef, k) <= " + std::to_string(MAX_REG_EF));
-    // exact search on the matrix cores (f32 rows: mfma_exact.hip, f16 rows: mfma_exact_f16.hip)
+    // exact search on the matrix cores (f32 rows: mfma_exact.hip, f16 / bf16 rows: mfma_exact_f16.hip)
     // when the batch amortises a query tile and the rows are whole 32-element groups
     const size_t mfma_min = (size_t)env_double("VSG_EXACT_MFMA_MIN", 32);
-    const size_t elem_bytes = h->st == ST_F16 ? 2 : 4;
+    const size_t elem_bytes = storage_elem_bytes(h->st);
     const bool mfma_shape = exact && (h->row_bytes / elem_bytes) % 32 == 0 && nq >= mfma_min && h->pub_slots > 0 &&
                             env_double("VSG_EXACT_MFMA", 1) != 0;
     // 17 <= k <= 128: the wide-k kernel (mfma_exact_wide.hip), from EXACT_WIDE_MIN_ROWS rows

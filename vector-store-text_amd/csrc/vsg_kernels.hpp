@@ -6,7 +6,9 @@
 
 namespace vsg {
 
-enum Storage { ST_F32 = 0, ST_F16 = 1 };
+enum Storage { ST_F32 = 0, ST_F16 = 1, ST_BF16 = 2 };  // the values of VSG_SCALAR_*
+// bytes per stored element
+inline size_t storage_elem_bytes(Storage st) { return st == ST_F32 ? 4 : 2; }
 enum MetricKind { MK_L2 = 0, MK_DOT = 1 };  // cos = DOT on normalised rows
 
 struct DevGraph {
@@ -153,13 +155,13 @@ struct MfmaExactParams {
     const float* ktile;
 };
 
-// Brute force on the f16 matrix cores (f16 storage, mfma_exact_f16.hip): the same
-// blocks, tiles and partial lists as MfmaExactParams over byte-addressed f16 rows of
-// row_bytes (a multiple of 64: whole 32-half groups); no K-tiled copy.
+// Brute force on the f16 / bf16 matrix cores (f16 or bf16 storage, mfma_exact_f16.hip): the
+// same blocks, tiles and partial lists as MfmaExactParams over byte-addressed 2-byte rows of
+// row_bytes (a multiple of 64: whole 32-element groups); no K-tiled copy.
 struct MfmaExactF16Params {
-    const uint8_t* vecs;     // N x row_bytes (stored f16 rows)
+    const uint8_t* vecs;     // N x row_bytes (stored f16 / bf16 rows)
     const float* sqnorm;     // N: |stored row|^2 (L2 only)
-    const uint8_t* queries;  // nq x row_bytes (prepared: rounded to f16)
+    const uint8_t* queries;  // nq x row_bytes (prepared: rounded to the storage type)
     const float* qsqnorm;    // nq: |prepared query|^2 (L2 only)
     int row_bytes;
     int nq;
@@ -178,11 +180,11 @@ struct MfmaExactF16Params {
 // of either storage; the selection is a threshold per query in LDS and a candidate pool
 // per (query, split) in device memory.  One sorted k-list per (query, split).
 struct MfmaExactWideParams {
-    const uint8_t* vecs;     // N x row_bytes (prepared f32 rows or stored f16 rows)
+    const uint8_t* vecs;     // N x row_bytes (prepared f32 rows or stored f16 / bf16 rows)
     const float* sqnorm;     // N (L2 only)
     const uint8_t* queries;  // nq x row_bytes (prepared)
     const float* qsqnorm;    // nq (L2 only)
-    int row_bytes;           // f32: a multiple of 128, f16: of 64
+    int row_bytes;           // f32: a multiple of 128, f16 / bf16: of 64
     int nq;
     size_t nslots;
     const uint8_t* flags;
@@ -298,9 +300,9 @@ constexpr int KTILE_ROWS = 256;
 // returns hipErrorNotSupported when the MFMA path does not apply (k > 32)
 hipError_t launch_mfma_exact(MetricKind mk, const MfmaExactParams& p, hipStream_t s);
 constexpr int MFMA_BQ = 128, MFMA_BR = 128;
-// the f16-storage sibling: hipErrorNotSupported for another tile or kmax,
-// hipErrorInvalidValue for rows that are not whole 32-half groups
-hipError_t launch_mfma_exact_f16(MetricKind mk, const MfmaExactF16Params& p, hipStream_t s);
+// the sibling of the 2-byte storages (st: ST_F16 or ST_BF16): hipErrorNotSupported for
+// another tile or kmax, hipErrorInvalidValue for rows that are not whole 32-element groups
+hipError_t launch_mfma_exact_f16(Storage st, MetricKind mk, const MfmaExactF16Params& p, hipStream_t s);
 // the wide-k sibling of both: hipErrorNotSupported outside 17 <= k <= MFMA_WIDE_MAX_K,
 // hipErrorInvalidValue for rows that are not whole 32-element groups
 hipError_t launch_mfma_exact_wide(Storage st, MetricKind mk, const MfmaExactWideParams& p, hipStream_t s);
