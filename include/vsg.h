@@ -70,6 +70,23 @@ extern "C" {
  *    VSG_FLAG_I8_TRAVERSAL and the K-tiled copy of exact-only indexes;
  *  - files store the rows as they are, with this value in the header. */
 #define VSG_SCALAR_BF16 2
+/* FP8 storage: OCP E4M3 "fn" -- 1 byte per element, 4 exponent bits (bias 7), 3 mantissa
+ * bits, largest finite value 448, no infinities.  Half the bytes of f16 and twice its
+ * matrix-core rate on gfx950; E4M3 x E4M3 products are exact in f32.  Contract of an FP8
+ * index (the bf16 one: round once, accumulate in f32):
+ *  - rows are rounded from f32 (after normalisation for cos) to the nearest E4M3 value,
+ *    ties to even; a finite value beyond +-448 (and +-inf) becomes +-448, NaN stays NaN,
+ *    subnormals (step 2^-9) are kept; export / get widen exactly, so export -> import is
+ *    the identity;
+ *  - queries arrive as f32 and are rounded the same way before any distance: every path
+ *    compares FP8 rows with FP8-rounded queries, accumulating in f32;
+ *  - exact-only indexes only: vsg_index_new with VSG_SCALAR_F8 and without
+ *    VSG_FLAG_EXACT_ONLY returns VSG_EUNSUPPORTED (no graph build or search over FP8
+ *    rows); the sketch prefilter, VSG_FLAG_F16_TRAVERSAL, VSG_FLAG_I8_TRAVERSAL and the
+ *    K-tiled copy do not apply, with the errors / silent non-use an f16 exact-only index
+ *    gives;
+ *  - files store the rows as they are, with this value in the header. */
+#define VSG_SCALAR_F8 3
 
 #define VSG_NO_KEY UINT64_MAX /* padding key for short result rows */
 
@@ -150,7 +167,7 @@ typedef struct {
     uint64_t search_i8_queries;        /* queries answered by the int8 walk (VSG_FLAG_I8_TRAVERSAL); its
                                           sketch rows also count in search_sketch_rows */
     uint64_t exact_mfma_queries;       /* exact-search queries answered by a matrix-core kernel (f32,
-                                          f16 or bf16 storage); the others took the VALU kernel */
+                                          f16, bf16 or FP8 storage); the others took the VALU kernel */
     uint64_t search_team_queries;      /* queries answered by the multi-wave search kernel
                                           (vsg_index_set_search_team) */
 } vsg_stats_t;
@@ -241,8 +258,10 @@ int vsg_index_search(vsg_index_t* index, const float* queries, size_t nq, size_t
  * f32 accumulation).  The same batches with 17 <= k <= 128 over at least 4,096 rows
  * (VSG_EXACT_WIDE_MIN_ROWS) run a third matrix-core kernel for either storage, which
  * selects through a per-query threshold and a candidate pool instead of a register
- * list.  Every other search (k > 128, fewer queries or rows, ragged dimensions) runs
- * the VALU kernel.  All return the top k by (distance, slot), equal up to f32 summation
+ * list.  FP8 storage (VSG_SCALAR_F8) runs the k <= 16 batches on the FP8 MFMA over rows
+ * of whole 64-element groups; it has no wide-k kernel, so 17 <= k <= 128 on FP8 rows
+ * stays on the VALU kernel.  Every other search (k > 128, fewer queries or rows, ragged
+ * dimensions) runs the VALU kernel.  All return the top k by (distance, slot), equal up to f32 summation
  * order; VSG_EXACT_MFMA=0 selects the VALU kernel, vsg_stats_t.exact_mfma_queries counts
  * the matrix-core queries. */
 int vsg_index_exact_search(vsg_index_t* index, const float* queries, size_t nq, size_t k,

@@ -25,6 +25,7 @@ pub const VSG_METRIC_COS: u32 = 2;
 pub const VSG_SCALAR_F32: u32 = 0;
 pub const VSG_SCALAR_F16: u32 = 1;
 pub const VSG_SCALAR_BF16: u32 = 2;
+pub const VSG_SCALAR_F8: u32 = 3;
 
 pub const VSG_NO_KEY: u64 = u64::MAX;
 pub const VSG_FLAG_EXACT_ONLY: u32 = 1;

@@ -117,12 +117,22 @@ hipError_t launch_exact(Storage st, MetricKind mk, const ExactParams& p, hipStre
     if (p.nq <= 0 || p.nblocks <= 0) return hipSuccess;
     const size_t lds = exact_lds_bytes(p.k);
     hipError_t err = hipSuccess;
-    dispatch_all(st, mk, p.nchunks, [&](auto sh, auto tt, auto mt) {
+    auto launch = [&](auto sh, auto tt, auto mt) {
         auto kern = VSG_KERNEL_OF(exact_kernel, sh, tt, mt);
         if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(p.nq, p.nblocks), dim3(64), lds, s, p);
         err = hipGetLastError();
-    });
+    };
+    if (st == ST_F8) {
+        // FP8 rows (exact-only indexes) exist for this kernel alone: dispatch_all would give
+        // every graph kernel an instance nothing can reach
+        dispatch_shape(p.nchunks, [&](auto sh) {
+            if (mk == MK_L2) launch(sh, TypeTag<f8_t>{}, MetTag<MET_L2>{});
+            else launch(sh, TypeTag<f8_t>{}, MetTag<MET_DOT>{});
+        });
+    } else {
+        dispatch_all(st, mk, p.nchunks, launch);
+    }
     return err;
 }
 

@@ -6,6 +6,7 @@
 // one-wave-per-row launch overflows beyond 2^32 / 64 = 67M rows (C4 is 100M).
 #include <hip/hip_runtime.h>
 
+#include "f8.hpp"
 #include "sketch.hpp"
 #include "vsg_device.hpp"
 #include "vsg_kernels.hpp"
@@ -26,8 +27,11 @@ static inline unsigned capped_grid(size_t items, size_t per_block, size_t cap = 
 // below, the midpoint; the carry runs on into the exponent, so a finite value beyond the
 // largest bf16 becomes inf and inf stays inf.  A NaN would turn into inf if its payload
 // sat in the dropped half only, so it keeps its upper half with the quiet bit set.
+// FP8 (E4M3): f8.hpp -- nearest even on the bits as well, saturating at +-448.
 template <typename T> __device__ __forceinline__ T to_storage(float v) {
-    if constexpr (std::is_same<T, bf16_t>::value) {
+    if constexpr (std::is_same<T, f8_t>::value) {
+        return f8_t{f8_encode(v)};
+    } else if constexpr (std::is_same<T, bf16_t>::value) {
         const uint32_t u = __float_as_uint(v);
         if ((u & 0x7fffffffu) > 0x7f800000u) return bf16_t{(uint16_t)((u >> 16) | 0x0040u)};
         return bf16_t{(uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16)};
@@ -36,7 +40,8 @@ template <typename T> __device__ __forceinline__ T to_storage(float v) {
     }
 }
 template <typename T> __device__ __forceinline__ float from_storage(T t) {
-    if constexpr (std::is_same<T, bf16_t>::value) return __uint_as_float((uint32_t)t.bits << 16);
+    if constexpr (std::is_same<T, f8_t>::value) return f8_decode(t.bits);
+    else if constexpr (std::is_same<T, bf16_t>::value) return __uint_as_float((uint32_t)t.bits << 16);
     else return (float)t;
 }
 
@@ -96,9 +101,12 @@ hipError_t launch_prepare(Storage st, const float* in, size_t n, int dim, bool n
     else if (st == ST_F16)
         hipLaunchKernelGGL(prepare_kernel<_Float16>, grid, dim3(256), 0, s, in, n, dim, normalize ? 1 : 0, out,
                            row_bytes, sqnorm);
-    else
+    else if (st == ST_BF16)
         hipLaunchKernelGGL(prepare_kernel<bf16_t>, grid, dim3(256), 0, s, in, n, dim, normalize ? 1 : 0, out,
                            row_bytes, sqnorm);
+    else
+        hipLaunchKernelGGL(prepare_kernel<f8_t>, grid, dim3(256), 0, s, in, n, dim, normalize ? 1 : 0, out, row_bytes,
+                           sqnorm);
     return hipGetLastError();
 }
 
@@ -111,8 +119,10 @@ hipError_t launch_unprepare(Storage st, const uint8_t* in, size_t n, int dim, si
         hipLaunchKernelGGL(unprepare_kernel<float>, grid, dim3(256), 0, s, in, n, dim, row_bytes, out);
     else if (st == ST_F16)
         hipLaunchKernelGGL(unprepare_kernel<_Float16>, grid, dim3(256), 0, s, in, n, dim, row_bytes, out);
-    else
+    else if (st == ST_BF16)
         hipLaunchKernelGGL(unprepare_kernel<bf16_t>, grid, dim3(256), 0, s, in, n, dim, row_bytes, out);
+    else
+        hipLaunchKernelGGL(unprepare_kernel<f8_t>, grid, dim3(256), 0, s, in, n, dim, row_bytes, out);
     return hipGetLastError();
 }
 

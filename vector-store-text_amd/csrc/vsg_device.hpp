@@ -34,8 +34,30 @@ struct bf16_t {
     uint16_t bits;
 };
 template <> struct ChunkT<bf16_t> { static constexpr int E = 8; };
+// FP8 storage tag: OCP E4M3 "fn" (1 sign, 4 exponent bits of bias 7, 3 mantissa bits; no
+// infinities, S.1111.111 is NaN, largest finite value 448).  Only ever widened.
+struct f8_t {
+    uint8_t bits;
+};
+template <> struct ChunkT<f8_t> { static constexpr int E = 16; };
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+typedef float float2_t __attribute__((ext_vector_type(2)));
+
+// 16-B chunk of FP8 storage -> 16 floats, exactly: gfx950's packed convert reads E4M3
+// (the OCP format on this target) and widens two bytes of a word per instruction.
+__device__ __forceinline__ void widen16_f8(const uint4 raw, float (&out)[16]) {
+    const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+        const float2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        out[4 * i] = lo[0];
+        out[4 * i + 1] = lo[1];
+        out[4 * i + 2] = hi[0];
+        out[4 * i + 3] = hi[1];
+    }
+}
 
 // 16-B chunk of a 2-byte storage type -> 8 floats, exactly.  f16: the packed converts;
 // bf16: each 32-bit word holds two elements whose f32 images are the word shifted up
@@ -66,6 +88,8 @@ __device__ __forceinline__ void load_chunk(const uint8_t* __restrict__ row, int 
         out[1] = __uint_as_float(raw.y);
         out[2] = __uint_as_float(raw.z);
         out[3] = __uint_as_float(raw.w);
+    } else if constexpr (sizeof(T) == 1) {
+        widen16_f8(raw, out);
     } else {
         widen8<T>(raw, out);
     }
@@ -205,6 +229,8 @@ template <int G, int VM, typename T> struct QReg {
                 x[v][1] = __uint_as_float(raw[v].y);
                 x[v][2] = __uint_as_float(raw[v].z);
                 x[v][3] = __uint_as_float(raw[v].w);
+            } else if constexpr (sizeof(T) == 1) {
+                widen16_f8(raw[v], x[v]);
             } else {
                 widen8<T>(raw[v], x[v]);
             }
@@ -216,7 +242,7 @@ template <int G, int VM, typename T> struct QReg {
     }
 };
 
-// 16-B chunk -> E floats (f16 / bf16 widened exactly to f32)
+// 16-B chunk -> E floats (f16 / bf16 / FP8 widened exactly to f32)
 template <typename T>
 __device__ __forceinline__ void unpack_chunk(const uint4 raw, float (&out)[ChunkT<T>::E]) {
     if constexpr (sizeof(T) == 4) {
@@ -224,6 +250,8 @@ __device__ __forceinline__ void unpack_chunk(const uint4 raw, float (&out)[Chunk
         out[1] = __uint_as_float(raw.y);
         out[2] = __uint_as_float(raw.z);
         out[3] = __uint_as_float(raw.w);
+    } else if constexpr (sizeof(T) == 1) {
+        widen16_f8(raw, out);
     } else {
         widen8<T>(raw, out);
     }

@@ -1526,14 +1526,17 @@ int vsg_index_new(const vsg_index_options_t* o, vsg_index_t** out) {
     *out = nullptr;
     if (o->dimensions == 0) return fail(VSG_EINVAL, "dimensions == 0");
     if (o->metric > VSG_METRIC_COS) return fail(VSG_EINVAL, "unknown metric");
-    if (o->quantization > VSG_SCALAR_BF16) return fail(VSG_EINVAL, "unknown quantization");
+    if (o->quantization > VSG_SCALAR_F8) return fail(VSG_EINVAL, "unknown quantization");
+    if (o->quantization == VSG_SCALAR_F8 && !(o->flags & VSG_FLAG_EXACT_ONLY))
+        return fail(VSG_EUNSUPPORTED, "FP8 storage (VSG_SCALAR_F8) supports exact-only indexes only: set VSG_FLAG_EXACT_ONLY "
+                                      "(graph build and search over FP8 rows are not implemented)");
     const uint32_t M = o->connectivity ? o->connectivity : 16;
     if (M < 2 || M > (uint32_t)MAX_CONNECTIVITY)
         return fail(VSG_EUNSUPPORTED, "connectivity must be in [2, " + std::to_string(MAX_CONNECTIVITY) + "]");
     auto* h = new vsg_index();
     h->opt = *o;
     h->dim = (int)o->dimensions;
-    h->st = o->quantization == VSG_SCALAR_F16 ? ST_F16 : o->quantization == VSG_SCALAR_BF16 ? ST_BF16 : ST_F32;
+    h->st = (Storage)o->quantization;  // ST_* are the values of VSG_SCALAR_*
     h->mk = o->metric == VSG_METRIC_L2SQ ? MK_L2 : MK_DOT;
     h->normalize = o->metric == VSG_METRIC_COS;
     h->M = (int)M;
@@ -1566,7 +1569,7 @@ int vsg_index_new(const vsg_index_options_t* o, vsg_index_t** out) {
     h->nchunks = (int)(h->row_bytes / 16);
     if (!shape_supported(h->nchunks)) {
         delete h;
-        return fail(VSG_EUNSUPPORTED, "dimensions too large (max 4096 f32 / 8192 f16, bf16)");
+        return fail(VSG_EUNSUPPORTED, "dimensions too large (max 4096 f32 / 8192 f16, bf16 / 16384 f8)");
     }
     h->device = o->device;
     int ndev = 0;
@@ -2368,8 +2371,8 @@ static hipError_t merge_parts_two_stage(float* pd, uint32_t* pi, const ExactPlan
     return launch_merge_parts(mp, s);
 }
 
-// f16 / bf16 storage: the stored rows against the queries prepared into the same type
-// (mfma_exact_f16.hip); same plan, partial lists and merge
+// f16 / bf16 / FP8 storage: the stored rows against the queries prepared into the same type
+// (mfma_exact_f16.hip, mfma_exact_f8.hip); same plan, partial lists and merge
 static int run_exact_mfma_f16(vsg_index* h, const SearchCall& c, const ExactPlan& plan, size_t slots) {
     float* pd = c.region<float>(c.at.part_d);
     uint32_t* pi = c.region<uint32_t>(c.at.part_i);
@@ -2390,7 +2393,7 @@ static int run_exact_mfma_f16(vsg_index* h, const SearchCall& c, const ExactPlan
     mp.br = plan.br;
     mp.part_d = pd;
     mp.part_i = pi;
-    hipError_t err = launch_mfma_exact_f16(h->st, h->mk, mp, c.s);
+    hipError_t err = h->st == ST_F8 ? launch_mfma_exact_f8(h->mk, mp, c.s) : launch_mfma_exact_f16(h->st, h->mk, mp, c.s);
     if (err == hipSuccess)
         err = merge_parts_two_stage(pd, pi, plan, c.nq, c.k, plan.kmax, h->d_keys, c.ok, c.od, c.oc, c.s);
     return search_launch_rc(err);
@@ -2667,15 +2670,18 @@ static int search_device_locked(vsg_index_t* h, const float* q_dev, size_t nq, s
     if (!exact && upper_ef > 1 && ef_eff > MAX_REG_EF)
         return fail(VSG_EUNSUPPORTED, "multi-entry descent (upper_ef) supports max(ef, k) <= " + std::to_string(MAX_REG_EF));
     // exact search on the matrix cores (f32 rows: mfma_exact.hip, f16 / bf16 rows: mfma_exact_f16.hip)
-    // when the batch amortises a query tile and the rows are whole 32-element groups
+    // when the batch amortises a query tile and the rows are whole 32-element groups (FP8 rows,
+    // mfma_exact_f8.hip: whole 64-element groups)
     const size_t mfma_min = (size_t)env_double("VSG_EXACT_MFMA_MIN", 32);
     const size_t elem_bytes = storage_elem_bytes(h->st);
-    const bool mfma_shape = exact && (h->row_bytes / elem_bytes) % 32 == 0 && nq >= mfma_min && h->pub_slots > 0 &&
+    const size_t mfma_group = h->st == ST_F8 ? 64 : 32;
+    const bool mfma_shape = exact && (h->row_bytes / elem_bytes) % mfma_group == 0 && nq >= mfma_min && h->pub_slots > 0 &&
                             env_double("VSG_EXACT_MFMA", 1) != 0;
     // 17 <= k <= 128: the wide-k kernel (mfma_exact_wide.hip), from EXACT_WIDE_MIN_ROWS rows
     // on -- the VALU kernel's own row block: below it a VALU launch is one block per query
     // with nothing to merge, and a threshold filter rejects little until rows >> k
-    const bool use_wide = mfma_shape && k > 16 && k <= (size_t)MFMA_WIDE_MAX_K &&
+    // (FP8 rows have no wide-k instance: 17 <= k <= 128 stays on the VALU kernel)
+    const bool use_wide = mfma_shape && h->st != ST_F8 && k > 16 && k <= (size_t)MFMA_WIDE_MAX_K &&
                           h->pub_slots >= (size_t)env_double("VSG_EXACT_WIDE_MIN_ROWS", EXACT_WIDE_MIN_ROWS);
     const bool use_mfma = (mfma_shape && k <= 16) || use_wide;
     const size_t slots = h->pub_slots;  // rows of the last completed add

@@ -6,9 +6,9 @@
 
 namespace vsg {
 
-enum Storage { ST_F32 = 0, ST_F16 = 1, ST_BF16 = 2 };  // the values of VSG_SCALAR_*
+enum Storage { ST_F32 = 0, ST_F16 = 1, ST_BF16 = 2, ST_F8 = 3 };  // the values of VSG_SCALAR_*
 // bytes per stored element
-inline size_t storage_elem_bytes(Storage st) { return st == ST_F32 ? 4 : 2; }
+inline size_t storage_elem_bytes(Storage st) { return st == ST_F32 ? 4 : st == ST_F8 ? 1 : 2; }
 enum MetricKind { MK_L2 = 0, MK_DOT = 1 };  // cos = DOT on normalised rows
 
 struct DevGraph {
@@ -303,6 +303,10 @@ constexpr int MFMA_BQ = 128, MFMA_BR = 128;
 // the sibling of the 2-byte storages (st: ST_F16 or ST_BF16): hipErrorNotSupported for
 // another tile or kmax, hipErrorInvalidValue for rows that are not whole 32-element groups
 hipError_t launch_mfma_exact_f16(Storage st, MetricKind mk, const MfmaExactF16Params& p, hipStream_t s);
+// the FP8 sibling (ST_F8, mfma_exact_f8.hip): the same parameters over 1-byte rows and
+// FP8-rounded queries; hipErrorNotSupported for another tile or kmax, hipErrorInvalidValue
+// for rows that are not whole 64-element groups (row_bytes % 64)
+hipError_t launch_mfma_exact_f8(MetricKind mk, const MfmaExactF16Params& p, hipStream_t s);
 // the wide-k sibling of both: hipErrorNotSupported outside 17 <= k <= MFMA_WIDE_MAX_K,
 // hipErrorInvalidValue for rows that are not whole 32-element groups
 hipError_t launch_mfma_exact_wide(Storage st, MetricKind mk, const MfmaExactWideParams& p, hipStream_t s);

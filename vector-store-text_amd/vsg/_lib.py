@@ -25,7 +25,7 @@ VSG_HELD = 6  # vsg_index_replace status: left unapplied under VSG_REPLACE_HOLD_
 VSG_REPLACE_HOLD_TAIL = 1
 
 METRICS = {"l2sq": 0, "ip": 1, "cos": 2}
-SCALARS = {"f32": 0, "f16": 1, "bf16": 2}
+SCALARS = {"f32": 0, "f16": 1, "bf16": 2, "f8": 3}
 NO_KEY = (1 << 64) - 1
 
 
